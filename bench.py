@@ -2,7 +2,7 @@
 """Headline benchmark: env-steps/sec of full GAIL rounds (generator rollout + PPO update +
 discriminator updates) on synthetic HalfCheetah-shaped data, BASELINE.json config[1].
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is ONE adversarial round (`AdversarialTrainer.train` body, reference
 `algorithms/adversarial/common.py:453-461`) at config P of SURVEY 8d: n_envs=1024 per GPU,
@@ -12,13 +12,20 @@ FeedForward32Policy + NormalizeFeaturesExtractor, minibatch 1024, 10 epochs. Hos
 (NumPy) stay on the CPU. For N>1 it runs one rank per GPU (env-batch sharded: 1024 envs per
 rank, weak scaling) with RCCL gradient / moment all-reduces every optimiser step.
 
-Prints ONE JSON line (rank 0). Extra objects: `roofline` for the kernel with the largest share of GPU
-time (the persistent PPO update: a latency chain, so its figure of merit is us_per_step), with the whole
-discriminator update (`disc_update`, the throughput kernel family SURVEY 8d's roofline target is about)
-and the GEMM family (`gemm`) as siblings, all measured with HIP events on the launch streams right
-after the timed region; `variants` = SURVEY 8d's other configurations through the same trainer;
-`cpu_baseline` = the oracle (CPU restatement of the reference round, torch CPU ops) timed on this box's
-host cores for a few rounds of the same workload.
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times the K rounds and prints the line
+(`value`, `ms_per_step`, the per-round spread). `--dump-outputs DIR` writes what the last timed round left
+behind -- trained policy and discriminator state, the round's rollout and replay tiles, reward
+predictions on a fixed seeded sample -- as DIR/<name>.npy (float32, or float64 for float64 and integer
+arrays): same arguments, same inputs, so two builds can be compared array for array.
+
+`--full` adds everything else, after the timed region: a longer sample (`--long-rounds`), `roofline` for
+the kernel with the largest share of GPU time (the persistent PPO update: a latency chain, so its figure
+of merit is us_per_step), with the whole discriminator update (`disc_update`, the throughput kernel
+family SURVEY 8d's roofline target is about) and the GEMM family (`gemm`) as siblings, all measured with
+HIP events on the launch streams (`--prof-rounds`); `variants` = SURVEY 8d's other configurations
+through the same trainer (`--no-variants` drops them); `cpu_baseline` = the oracle (CPU restatement of
+the reference round, torch CPU ops) timed on the host cores for a few rounds of the same workload
+(`--no-cpu-baseline` drops it). Without `--full` those fields of the line are null.
 """
 from __future__ import annotations
 
@@ -606,6 +613,43 @@ def _dp_form_text(algo):
     return "row-sharded / replicated alternating (the timed trials were not over)"
 
 
+DUMP_SAMPLE_ROWS = 4096   # reward queries on a fixed seeded sample of inputs
+
+
+def dump_outputs(trainer, cfg, out_dir):
+    """What the timed path hands a caller after its last round, one `.npy` per array: discriminator and policy state,
+    the last rollout tile, the generator replay ring, and both reward functions on a seeded sample (a few MB in all)."""
+    th.cuda.synchronize()
+    arrays = {}
+    for k, v in trainer._reward_net.state_dict().items():
+        arrays[f"disc.{k}"] = v
+    for k, v in trainer.gen_algo.policy.state_dict().items():
+        arrays[f"policy.{k}"] = v
+    rb = trainer.gen_algo.rollout_buffer
+    for k in ("rewards", "values", "log_probs", "advantages", "returns", "actions", "observations"):
+        arrays[f"rollout.{k}"] = getattr(rb, k)
+    buf = trainer._gen_replay_buffer
+    ring = buf._buffer._arrays if hasattr(buf, "_buffer") else buf._arrays
+    for k in ("obs", "acts", "next_obs", "dones"):
+        arrays[f"replay.{k}"] = ring[k]
+    rng = np.random.default_rng(7)
+    n = DUMP_SAMPLE_ROWS
+    s = rng.standard_normal((n, cfg["obs_dim"])).astype(np.float32)
+    a = rng.uniform(-1, 1, (n, cfg["act_dim"])).astype(np.float32)
+    ns_ = rng.standard_normal((n, cfg["obs_dim"])).astype(np.float32)
+    d = rng.random(n) < 0.2
+    arrays["reward_train_predict"] = trainer.reward_train.predict(s, a, ns_, d)
+    arrays["reward_test_predict"] = trainer.reward_test.predict(s, a, ns_, d)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, x in arrays.items():
+        x = x.detach().cpu().numpy() if isinstance(x, th.Tensor) else np.asarray(x)
+        x = x.astype(np.float64 if x.dtype == np.float64 or x.dtype.kind in "biu" else np.float32)
+        total += x.nbytes
+        np.save(os.path.join(out_dir, name.replace("/", ".") + ".npy"), x)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
 def _self_launch(n_gpus: int) -> int:
     """`python bench.py --gpus N` without a launcher's environment: re-runs this file under
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` with the same arguments
@@ -629,11 +673,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)   # ~1 s of timed rounds at config P
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed round computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the longer sample, the roofline records, the variants and the CPU baselines")
+    # (the four below apply to --full runs only)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--prof-rounds", type=int, default=2)
     ap.add_argument("--no-variants", action="store_true")
     ap.add_argument("--long-rounds", type=int, default=200)   # total rounds of the longer sample behind the timed region
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run on this
@@ -702,9 +753,11 @@ def main():
                   "note": "host time stamps at the end of each round's iteration inside the ONE timed train() call; "
                           "under the pipelined schedule a stamp leads the device by up to one round's updates, so single "
                           "gaps are indicative and their sum is what `ms_per_step` measures"}
-    # ... and a longer sample right behind the timed region, so that K x 3.8 ms is never the only number: the same call
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, cfg, args.dump_outputs)   # before --full trains the same trainer further
+    # --full: a longer sample right behind the timed region, so that K x 3.8 ms is never the only number: the same call
     # over `--long-rounds` rounds (default 200 minus K), timed the same way; `value_long` covers both regions together
-    long_rounds = max(0, args.long_rounds - args.steps)
+    long_rounds = max(0, args.long_rounds - args.steps) if args.full else 0
     value_long = None
     if long_rounds > 0:
         barrier()
@@ -718,11 +771,11 @@ def main():
 
     # the profiled rounds are training rounds too: under data parallelism EVERY rank must take part in
     # their collectives (only rank 0's measurement is reported)
-    roof = gemm_roofline(trainer, cfg, args.prof_rounds) if args.prof_rounds > 0 else None
+    roof = gemm_roofline(trainer, cfg, args.prof_rounds) if args.full and args.prof_rounds > 0 else None
     if rank != 0:
         roof = None
     variants = None
-    if rank == 0 and world == 1 and not args.no_variants:
+    if args.full and rank == 0 and world == 1 and not args.no_variants:
         # SURVEY 8d's other configurations through the same trainer (a few rounds each, after the timed region)
         variants = {}
         for name in VARIANTS:
@@ -731,7 +784,7 @@ def main():
             except Exception as e:  # a variant must never take the headline down with it
                 variants[name] = {"error": f"{type(e).__name__}: {e}"}
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base = cpu_baseline(cfg, host_threads)
         if variants:
             for name in CPU_VARIANTS:   # the oracle beside the reference's shipped configurations (one round each)

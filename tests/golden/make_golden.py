@@ -126,6 +126,8 @@ def main():
         print(f"wrote {path}: {len(out)} arrays, {os.path.getsize(path)} bytes")
     dump_bc()
     dump_cnn_reward_net()
+    dump_cnn_reward_net_variants()
+    dump_expert_rollouts()
 
 
 def dump_bc():
@@ -161,6 +163,67 @@ def dump_cnn_reward_net():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def dump_cnn_reward_net_variants():
+    """`CnnRewardNet` of the reference for each constructor variant of `tests/test_oracle_pinning.py`
+    (`CNN_REWARD_NET_KWS`), from `torch.manual_seed(3)`: digests of the initial parameters and `predict_processed` on
+    seeded uint8 frames (`cnn_reward_net_variants.json`)."""
+    import json
+
+    import torch
+
+    from imitation_amd import spaces
+    from oracle import ref_shim
+    from tests.test_oracle_pinning import CNN_REWARD_NET_KWS, cnn_reward_net_inputs
+
+    ref_shim.install()
+    from imitation.rewards import reward_nets as rrn
+
+    out = []
+    for kw in CNN_REWARD_NET_KWS:
+        osp, asp, args = cnn_reward_net_inputs(kw)
+        torch.manual_seed(3)
+        net = rrn.CnnRewardNet(osp, asp, **kw)
+        rews = np.asarray(net.predict_processed(*args))
+        out.append(dict(kw={k: list(v) if isinstance(v, tuple) else v for k, v in kw.items()},
+                        state_dict={k: harness.array_digest(v.numpy()) for k, v in net.state_dict().items()},
+                        rews_dtype=rews.dtype.str, rews=[float(x) for x in rews]))
+    path = os.path.join(HERE, "cnn_reward_net_variants.json")
+    with open(path, "w") as f:
+        json.dump(out, f)
+    print("wrote", path)
+
+
+EXPERT_FIXTURES = ("cartpole_0", "pendulum_0")
+
+
+def dump_expert_rollouts():
+    """The reference's expert rollouts (`tests/testdata/expert_models/<name>/rollouts/final.npz`, legacy layout) copied
+    to `expert_rollouts/<name>.npz`, and digests of what the reference's own `serialize.load` decodes from the copies
+    (`expert_rollouts/decoded_by_reference.json`)."""
+    import json
+    import shutil
+    import warnings
+
+    from oracle import ref_shim
+
+    ref_shim.install()
+    from imitation.data import serialize as rser
+
+    out_dir = os.path.join(HERE, "expert_rollouts")
+    os.makedirs(out_dir, exist_ok=True)
+    testdata = os.path.join(os.path.dirname(ref_shim.REFERENCE_SRC), "tests", "testdata", "expert_models")
+    digests = {}
+    for name in EXPERT_FIXTURES:
+        path = os.path.join(out_dir, f"{name}.npz")
+        shutil.copyfile(os.path.join(testdata, name, "rollouts", "final.npz"), path)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            digests[name] = harness.trajectory_digests(rser.load(path))
+    with open(os.path.join(out_dir, "decoded_by_reference.json"), "w") as f:
+        json.dump(digests, f)
+    print("wrote", out_dir, {k: len(v) for k, v in digests.items()})
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "bc":        # one BC case: make_golden.py bc <name>
         out = harness.run_bc_case("reference", sys.argv[2], tempfile.mkdtemp())
@@ -170,6 +233,10 @@ if __name__ == "__main__":
         dump_cnn_reward_net()
     elif len(sys.argv) > 1 and sys.argv[1] == "bc":
         dump_bc()
+    elif len(sys.argv) > 1 and sys.argv[1] == "expert_rollouts":
+        dump_expert_rollouts()
+    elif len(sys.argv) > 1 and sys.argv[1] == "cnn_reward_variants":
+        dump_cnn_reward_net_variants()
     elif len(sys.argv) > 2 and sys.argv[1] == "case":      # one training case: make_golden.py case <name>
         out = harness.run_case("reference", sys.argv[2], tempfile.mkdtemp())
         np.savez_compressed(os.path.join(HERE, f"{sys.argv[2]}.npz"), **out)

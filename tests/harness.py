@@ -376,6 +376,21 @@ def run_case(impl: str, name: str, log_dir: str, device: str = "cpu", sync_disc:
     return out
 
 
+def array_digest(x) -> list:
+    """dtype, shape and sha256 of the bytes of an array: equal digests, bit-identical arrays."""
+    import hashlib
+
+    x = np.ascontiguousarray(np.asarray(x))
+    return [x.dtype.str, list(x.shape), hashlib.sha256(x.tobytes()).hexdigest()]
+
+
+def trajectory_digests(trajs) -> list:
+    """Per trajectory: `array_digest` of `obs`, `acts`, `rews`, and `terminal` -- two decodes with equal digests are
+    bit-identical (tests/golden/expert_rollouts/decoded_by_reference.json)."""
+    return [dict(obs=array_digest(t.obs), acts=array_digest(t.acts), rews=array_digest(t.rews), terminal=bool(t.terminal))
+            for t in trajs]
+
+
 # Keys whose values are integer/boolean bookkeeping and must match bit-exactly.
 EXACT_KEYS = ("replay/dones", "replay/_idx", "replay/_n_data", "counters")
 

@@ -672,7 +672,7 @@ def test_bench_two_rank_launch_line_on_one_gpu(tmp_path):
     env = dict(os.environ, IA_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "2", "--prof-rounds", "1"]
+           "--warmup", "2", "--prof-rounds", "1", "--full"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-4000:]
     line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]
@@ -713,7 +713,7 @@ def test_bench_bare_command_launches_its_own_ranks(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = _bench_line(tmp_path, [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup",
-                                 "5", "--prof-rounds", "1"])
+                                 "5", "--prof-rounds", "1", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["value"] > 0 and out["config"]["parallelism"] == "dp2"
     ch = out["config"]["ppo_update_choice"]   # five warm-up rounds: the four timed trials and the verdict
     assert ch is not None and ch["chosen"] in ("sharded", "replicated")
@@ -732,7 +732,7 @@ def test_bench_failed_peer_handshake_lands_every_rank_on_the_replicated_update(t
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = _bench_line(tmp_path, [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup",
-                                 "2", "--prof-rounds", "1"], extra_env={"IA_PEER_FAIL_RANK": "1"})
+                                 "2", "--prof-rounds", "1", "--full"], extra_env={"IA_PEER_FAIL_RANK": "1"})
     assert out["n_gpus"] == 2 and out["value"] > 0
     by_rank = out["config"]["ppo_update_by_rank"]
     assert len(by_rank) == 2

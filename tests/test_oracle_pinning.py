@@ -215,34 +215,56 @@ def test_trainer_error_contract(tmp_path):
         at.logits_expert_is_high(th.zeros(2, 11), th.zeros(2, 3), th.zeros(2, 11), th.zeros(2), None)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference not present")
-@pytest.mark.parametrize("kw", [dict(), dict(use_next_state=True, use_done=True), dict(use_action=False),
-                                dict(use_action=False, use_done=True, hwc_format=False, hid_channels=(8,))])
-def test_cnn_reward_net_bit_identical_to_live_reference(kw):
-    """`CnnRewardNet` / `build_cnn` (rewards/reward_nets.py:460-610, util/networks.py:286-357): same parameters
-    from the same seed, same forward values, same `predict_processed` on uint8 frames, same errors."""
-    ref_shim.install()
-    from imitation.rewards import reward_nets as rrn
+CNN_REWARD_NET_KWS = [dict(), dict(use_next_state=True, use_done=True), dict(use_action=False),
+                      dict(use_action=False, use_done=True, hwc_format=False, hid_channels=(8,))]
 
+
+def cnn_reward_net_inputs(kw):
+    """Spaces and seeded `predict_processed` arguments (7 uint8 frames) for one `CnnRewardNet` variant."""
     from imitation_amd import spaces
-    from oracle import imitation_restated as o
 
-    hwc = kw.get("hwc_format", True)
-    shape = (12, 10, 3) if hwc else (3, 12, 10)
-    osp, asp = spaces.Box(0, 255, shape, np.uint8), spaces.Discrete(5)
-    th.manual_seed(3)
-    a = rrn.CnnRewardNet(osp, asp, **kw)
-    th.manual_seed(3)
-    b = o.CnnRewardNet(osp, asp, **kw)
-    sa, sb_ = a.state_dict(), b.state_dict()
-    assert list(sa) == list(sb_) and all(th.equal(sa[k], sb_[k]) for k in sa)
+    shape = (12, 10, 3) if kw.get("hwc_format", True) else (3, 12, 10)
     rng = np.random.default_rng(0)
     obs = rng.integers(0, 256, (7, *shape), dtype=np.uint8)
     nxt = rng.integers(0, 256, (7, *shape), dtype=np.uint8)
     acts, dones = rng.integers(0, 5, 7), rng.random(7) < 0.5
-    assert np.array_equal(a.predict_processed(obs, acts, nxt, dones), b.predict_processed(obs, acts, nxt, dones))
-    for net in (rrn.CnnRewardNet, o.CnnRewardNet):
+    return spaces.Box(0, 255, shape, np.uint8), spaces.Discrete(5), (obs, acts, nxt, dones)
+
+
+@pytest.mark.parametrize("kw", CNN_REWARD_NET_KWS)
+def test_cnn_reward_net_bit_identical_to_live_reference(kw):
+    """`CnnRewardNet` / `build_cnn` (rewards/reward_nets.py:460-610, util/networks.py:286-357): same parameters
+    from the same seed, same forward values, same `predict_processed` on uint8 frames, same errors. Against the
+    reference's own net where it is present; elsewhere against what it produced (tests/golden/
+    cnn_reward_net_variants.json: parameter digests, bit for bit; predictions within the golden tolerance)."""
+    from imitation_amd import spaces
+    from oracle import imitation_restated as o
+
+    osp, asp, args = cnn_reward_net_inputs(kw)
+    th.manual_seed(3)
+    b = o.CnnRewardNet(osp, asp, **kw)
+    sb_ = b.state_dict()
+    nets = [o.CnnRewardNet]
+    if ref_shim.reference_available():
+        ref_shim.install()
+        from imitation.rewards import reward_nets as rrn
+
+        th.manual_seed(3)
+        a = rrn.CnnRewardNet(osp, asp, **kw)
+        sa = a.state_dict()
+        assert list(sa) == list(sb_) and all(th.equal(sa[k], sb_[k]) for k in sa)
+        assert np.array_equal(a.predict_processed(*args), b.predict_processed(*args))
+        nets.insert(0, rrn.CnnRewardNet)
+    else:
+        with open(os.path.join(GOLDEN, "cnn_reward_net_variants.json")) as f:
+            gold = json.load(f)[CNN_REWARD_NET_KWS.index(kw)]
+        assert gold["kw"] == {k: list(v) if isinstance(v, tuple) else v for k, v in kw.items()}
+        assert {k: harness.array_digest(v.numpy()) for k, v in sb_.items()} == gold["state_dict"]
+        assert list(sb_) == list(gold["state_dict"])
+        got = np.asarray(b.predict_processed(*args))
+        assert got.dtype.str == gold["rews_dtype"]
+        np.testing.assert_allclose(got, np.asarray(gold["rews"], dtype=got.dtype), rtol=1e-5, atol=1e-6)
+    for net in nets:
         with pytest.raises(ValueError, match="current or next state"):
             net(osp, asp, use_state=False, use_next_state=False)
         with pytest.raises(ValueError, match="to be images"):

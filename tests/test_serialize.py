@@ -104,22 +104,33 @@ def test_cross_read_with_live_reference(tmp_path):
         assert a.obs.dtype == b.obs.dtype == c.obs.dtype and a.rews.dtype == b.rews.dtype == c.rews.dtype
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="/root/reference not present")
 @pytest.mark.parametrize("fixture", ["cartpole_0", "pendulum_0"])
 def test_reference_expert_fixtures_decode_identically(fixture):
     """The reference's own expert rollouts (`tests/testdata/expert_models/*/rollouts/final.npz`,
-    legacy layout): same trajectories as its loader returns."""
-    ref_shim.install()
-    from imitation.data import serialize as rser
+    legacy layout, copied to `tests/golden/expert_rollouts/`): same trajectories, bit for bit and
+    dtype for dtype, as its loader returns -- digests of its decode in `decoded_by_reference.json`
+    (`make_golden.py expert_rollouts`), and its loader run live where the reference is present."""
+    import json
 
-    path = f"/root/reference/tests/testdata/expert_models/{fixture}/rollouts/final.npz"
+    from tests import harness
+
+    path = os.path.join(GOLDEN, "expert_rollouts", f"{fixture}.npz")
+    with open(os.path.join(GOLDEN, "expert_rollouts", "decoded_by_reference.json")) as f:
+        theirs = json.load(f)[fixture]
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        theirs, mine = rser.load(path), ser.load(path)
+        mine = ser.load(path)
     assert len(theirs) == len(mine) >= 56
-    for a, b in zip(theirs, mine):
-        _same(a, b)
-        assert a.obs.dtype == b.obs.dtype and a.acts.dtype == b.acts.dtype
+    assert harness.trajectory_digests(mine) == theirs
+    if ref_shim.reference_available():
+        ref_shim.install()
+        from imitation.data import serialize as rser
+
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            live = rser.load(path)
+        for a, b in zip(live, mine):
+            _same(a, b)
+            assert a.obs.dtype == b.obs.dtype and a.acts.dtype == b.acts.dtype
     flat = ser.load_transitions(path)
-    assert len(flat) == sum(len(t.acts) for t in theirs)
+    assert len(flat) == sum(len(t.acts) for t in mine)

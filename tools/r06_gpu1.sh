@@ -6,7 +6,7 @@ mkdir -p $O
 timeout 1500 python -m pytest tests/test_distributed.py -m gpu -x -q --durations=20 > $O/dist.log 2>&1; echo "dist rc=$?" | tee -a $O/rc.txt
 timeout 900 python -m pytest tests/test_adversarial_gpu.py -m gpu -x -q -k "round_draws or pipelined" > $O/adv.log 2>&1; echo "adv rc=$?" | tee -a $O/rc.txt
 timeout 900 python -m pytest tests/test_kernels_gpu.py -m gpu -x -q -k "word_exchange" > $O/kern.log 2>&1; echo "kern rc=$?" | tee -a $O/rc.txt
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/rc.txt
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/rc.txt
 tail -5 $O/dist.log; tail -3 $O/adv.log; tail -3 $O/kern.log
 python - <<'PY'
 import json
