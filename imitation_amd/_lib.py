@@ -242,6 +242,9 @@ _SIGS = {
     "ia_peer_ipc_open": ([_P, C.POINTER(C.c_void_p)], C.c_int),
     "ia_peer_ipc_close": ([_P], C.c_int),
     "ia_peer_handshake": ([_I, _I, C.c_uint32, _P, _P, _D, _P, _P], C.c_int),
+    "ia_kde_tile_rows": ([_I], C.c_int),
+    "ia_kde_slabs": ([_L, _I], C.c_int),
+    "ia_kde_log_density": ([_I, _D, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

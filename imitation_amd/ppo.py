@@ -746,6 +746,15 @@ class PPO(OnPolicyAlgorithm):
             if (isinstance(owner, _modules.RewardNet) and getattr(rw.reward_fn, "__name__", "") == "predict_processed"
                     and _modules.bulk_relabel_ok(owner)):
                 module_net = owner
+        # a stationary `DensityAlgorithm` (class without its own `__call__`): a row's reward does not depend on the batch it
+        # is scored in, so the whole [T, n] tile is relabelled by one kernel density call behind the last step, with the
+        # bits the per-step calls give (a non-stationary model needs the steps' timesteps: it keeps the per-step call)
+        density = None
+        if rw is not None and fused_net is None and module_net is None:
+            from imitation_amd.density import DensityAlgorithm
+            fn = rw.reward_fn
+            if isinstance(fn, DensityAlgorithm) and type(fn).__call__ is DensityAlgorithm.__call__ and fn.is_stationary:
+                density = fn
         T, n = rb.buffer_size, rb.n_envs
         assert n_rollout_steps == T
         if hasattr(base, "set_lookahead"):  # host env that can draw its noise one rollout ahead (SyntheticVecEnv)
@@ -779,7 +788,8 @@ class PPO(OnPolicyAlgorithm):
         host_sampling = pol.samples_on_host  # Discrete head on the reference's torch.multinomial stream
         predrawn = False
         mailbox = None
-        hooked = _has_user_step_hook(callback) or (rw is not None and fused_net is None and module_net is None)
+        hooked = _has_user_step_hook(callback) or (rw is not None and fused_net is None and module_net is None
+                                                    and density is None)
         mb_timeout = min(self.rollout_mailbox_timeout_s, self.rollout_mailbox_hooked_timeout_s) if hooked \
             else self.rollout_mailbox_timeout_s
         with th.cuda.stream(act_stream):
@@ -820,7 +830,8 @@ class PPO(OnPolicyAlgorithm):
         try:
             return self._rollout_steps(env, callback, rb, T, n, pol, rw, bw, base, fused_net, module_net, act_step, mailbox,
                                        act_stream, host_sampling, predrawn, starts, per_step_rews, prof, tick, h_clip_np,
-                                       h_rew_np, h_dones_np, h_trunc_np, h_next_np, h_obs_np, h_starts_np, stream)
+                                       h_rew_np, h_dones_np, h_trunc_np, h_next_np, h_obs_np, h_starts_np, stream,
+                                       density=density)
         finally:
             if mailbox is not None:
                 mailbox[2]()
@@ -887,7 +898,7 @@ class PPO(OnPolicyAlgorithm):
 
     def _rollout_steps(self, env, callback, rb, T, n, pol, rw, bw, base, fused_net, module_net, act_step, mailbox,
                        act_stream, host_sampling, predrawn, starts, per_step_rews, prof, tick, h_clip_np, h_rew_np,
-                       h_dones_np, h_trunc_np, h_next_np, h_obs_np, h_starts_np, stream) -> bool:
+                       h_dones_np, h_trunc_np, h_next_np, h_obs_np, h_starts_np, stream, density=None) -> bool:
         """The step loop and the tail of `collect_rollouts` (its own function so that the rollout mailbox is closed on
         every way out)."""
         # Mailbox rollouts post step t + 1 AS SOON AS its observations are in their pinned row -- ahead of the rest of step
@@ -957,7 +968,8 @@ class PPO(OnPolicyAlgorithm):
                 bw.record_step(acts_np, new_obs, nxt, env_rews, dones, infos)
             h_next_np[t] = nxt.reshape(n, -1)
             h_dones_np[t], h_trunc_np[t], h_starts_np[t] = dones, trunc, starts
-            if rw is not None and fused_net is None and module_net is None:  # arbitrary host reward function: per-step call
+            if rw is not None and fused_net is None and module_net is None and density is None:
+                # arbitrary host reward function: per-step call
                 r = rw.reward_fn(old_obs, acts_np, nxt, np.array(dones))
                 per_step_rews.append(np.asarray(r, dtype=np.float32))
                 h_rew_np[t] = per_step_rews[-1]
@@ -1024,10 +1036,13 @@ class PPO(OnPolicyAlgorithm):
             rb.rew.copy_(fused_net.predict_processed_rollout(table, T, n).reshape(T, n))
         elif module_net is not None:
             self._relabel_module_rows(rb, module_net, pol, early_T * n, T * n, T, n)
+        elif density is not None:
+            density.relabel_rollout(rb.obs[:T], rb.clipped, rb.next_fixed, rb.rew, pol.discrete)
         else:
             rb.rew.copy_(rb.h_rew, non_blocking=True)
         if rw is not None:
-            if (fused_net is not None or module_net is not None) and self.enqueue_first:
+            relabelled = fused_net is not None or module_net is not None or density is not None
+            if relabelled and self.enqueue_first:
                 # episode-return bookkeeping needs the relabelled rewards on the host but nothing on the
                 # device needs it: copy now, consume after the PPO update has been enqueued
                 rb.h_rew.copy_(rb.rew, non_blocking=True)
@@ -1041,8 +1056,7 @@ class PPO(OnPolicyAlgorithm):
 
                 self._post_enqueue_work.append(bookkeeping)
             else:
-                wrapped = (rb.rew.cpu().numpy() if (fused_net is not None or module_net is not None)
-                           else np.stack(per_step_rews))
+                wrapped = rb.rew.cpu().numpy() if relabelled else np.stack(per_step_rews)
                 rw.record_rewards(wrapped, h_dones_np.astype(bool), self._last_obs)
         if h_trunc_np.any():  # rewards[i] += gamma * V(terminal_obs_i) for time-limit endings
             pol.values_rows(rb.next_fixed.reshape(T * n, -1), rb.term_val.reshape(T * n))

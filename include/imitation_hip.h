@@ -777,6 +777,26 @@ int ia_peer_ipc_close(void* p);
 int ia_peer_handshake(int world, int rank, uint32_t token, uint32_t* own_words, uint32_t* const* peer_words,
                       double timeout_s, int* result, void* stream);
 
+/* Kernel density of the density baseline (algorithms/density.py:256-263 `_fit_density`, :295-360 `__call__`:
+ * sklearn.neighbors.KernelDensity(kernel, bandwidth=h).score_samples, Euclidean metric): for query row x of group g,
+ *   out[row] = log sum_{i < demo_n[g]} K_h(|std(x) - Y[demo_off[g] + i]|) + gconst[g],   gconst[g] = c(h, d, kernel) - log N_g
+ * with std(x) = float(float(x - mean) / scale), each step in double (StandardScaler.transform on float32 rows), computed
+ * in the kernel. kernel: 0 gaussian, 1 tophat, 2 epanechnikov, 3 exponential, 4 linear, 5 cosine (compact kernels: -inf where
+ * no demo is within h, never NaN). Y[*, ldy]: standardised fp32 demo rows, groups contiguous; ynorm: their squared norms;
+ * demo_off int64 [G], demo_n int32 [G] (>= 1), gconst double [G]; Q[n_q, d]: raw query rows in the caller's order; mean /
+ * scale double [d]; perm int32 [n_q]: sorted position -> caller's row (NULL: identity); tiles int32 [n_tiles][3]: (first
+ * sorted position, rows <= ia_kde_tile_rows(d), group) -- the query rows sorted stably by group, cut per group.
+ * partials: float workspace [max_slabs][n_q][2], max_slabs >= ia_kde_slabs(demo_n[g], d) of every group. A group's demos
+ * are cut into slabs by a rule of N_g alone and the slabs' (max, sum) merged in slab order, so a row's result does not
+ * depend on the batch it is scored in. stages: 1 the slab kernel, 2 the merge (into out, scattered through perm), 3 both.
+ * IA_ERR_ARG for bad shapes or an unknown kernel code; IA_ERR_UNSUPPORTED when the query tile of d does not fit in LDS. */
+int ia_kde_tile_rows(int d);
+int ia_kde_slabs(int64_t n_demo, int d);
+int ia_kde_log_density(int kernel, double h, int d, const float* Y, int ldy, const float* ynorm, const int64_t* demo_off,
+                       const int* demo_n, const double* gconst, int max_slabs, const float* Q, int n_q, const double* mean,
+                       const double* scale, const int* perm, const int* tiles, int n_tiles, float* partials, float* out,
+                       int stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
