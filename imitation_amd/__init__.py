@@ -22,7 +22,8 @@ from imitation_amd.adversarial.common import AdversarialTrainer, compute_train_s
 from imitation_amd.adversarial.gail import GAIL, RewardNetFromDiscriminatorLogit  # noqa: F401
 from imitation_amd.adversarial.airl import AIRL  # noqa: F401
 from imitation_amd.density import DensityAlgorithm, DensityType  # noqa: F401
-from imitation_amd import bc, checkpoint, cnn_policy, density, modules, ops, rollout, serialize  # noqa: F401
+from imitation_amd import (bc, checkpoint, cnn_policy, density, modules, ops, preference_comparisons,  # noqa: F401
+                           rollout, serialize)
 
 
 def configure_logger(folder=None, format_strs=None):

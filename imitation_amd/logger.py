@@ -137,6 +137,9 @@ class Logger:
     def log(self, *args, **kwargs) -> None:
         pass
 
+    def warn(self, *args, **kwargs) -> None:
+        """SB3 `Logger.warn` (the reference's fragmenter calls it); like `log`, nothing is written."""
+
     def close(self) -> None:
         for w in self.output_formats:
             w.close()
@@ -187,6 +190,11 @@ class HierarchicalLogger(Logger):
             yield
         finally:
             self._accumulate_prefixes.pop()
+
+    def get_accumulate_prefixes(self) -> str:
+        """`util/logger.py:188-190`."""
+        prefixes = "/".join(self._accumulate_prefixes)
+        return prefixes + "/" if prefixes else ""
 
     @contextlib.contextmanager
     def add_key_prefix(self, prefix: str):

@@ -388,12 +388,14 @@ def gather_concat(table: TransitionTable, idx: Optional[th.Tensor], n: int, obs_
 
 class HipAdam:
     """`torch.optim.Adam` (single param group) over one flat device buffer, stepping with the
-    fused HIP kernel. Mirrors the constructor kwargs and `state_dict` fields that matter."""
+    fused HIP kernel. Mirrors the constructor kwargs and `state_dict` fields that matter.
+    `decoupled=True`: `torch.optim.AdamW` (`p *= 1 - lr * weight_decay` before the Adam update; host-stepped only)."""
 
     def __init__(self, flat: th.Tensor, grad: th.Tensor, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, amsgrad: bool = False, **unused):
+                 weight_decay: float = 0.0, amsgrad: bool = False, decoupled: bool = False, **unused):
         if amsgrad:
             raise NotImplementedError("amsgrad is not implemented on the HIP path")
+        self.decoupled = bool(decoupled)
         self.flat, self.grad = flat, grad
         self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)]
         self.exp_avg = th.zeros_like(flat)
@@ -408,6 +410,8 @@ class HipAdam:
         """From here on `step()` takes its bias-correction scalars from a device-side step count (two launches per
         step, no host-dependent kernel arguments), so a captured sequence of steps can be replayed; the host count is
         advanced by the caller (`end_device_steps`)."""
+        if self.decoupled:
+            raise NotImplementedError("device-counted steps are not implemented for AdamW")
         if getattr(self, "_dev_step", None) is None:
             self._dev_step = th.zeros(1, dtype=th.int64, device=self.flat.device)
             self._dev_scal = th.zeros(2, device=self.flat.device)
@@ -438,6 +442,11 @@ class HipAdam:
         b1, b2 = g["betas"]
         bc1 = 1.0 - b1 ** self.step_count
         bc2 = 1.0 - b2 ** self.step_count
+        if self.decoupled:
+            L.call("ia_adamw_step", L.ptr(self.flat), L.ptr(self.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                   self.flat.numel(), b1, b2, g["eps"], 1.0 - g["lr"] * g["weight_decay"], g["lr"] / bc1, bc2 ** 0.5,
+                   L.stream())
+            return
         L.call("ia_adam_step", L.ptr(self.flat), L.ptr(self.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
                self.flat.numel(), b1, b2, g["eps"], g["weight_decay"], g["lr"] / bc1, bc2 ** 0.5, L.stream())
 
@@ -448,6 +457,11 @@ class HipAdam:
         b1, b2 = g["betas"]
         bc1 = 1.0 - b1 ** self.step_count
         bc2 = 1.0 - b2 ** self.step_count
+        if self.decoupled:
+            L.call("ia_reduce_partials_adamw", L.ptr(partials), splits, self.flat.numel(), scale, L.ptr(self.grad),
+                   L.ptr(self.flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), b1, b2, g["eps"],
+                   1.0 - g["lr"] * g["weight_decay"], g["lr"] / bc1, bc2 ** 0.5, L.stream())
+            return
         L.call("ia_reduce_partials_adam", L.ptr(partials), splits, self.flat.numel(), scale, L.ptr(self.grad),
                L.ptr(self.flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), b1, b2, g["eps"], g["weight_decay"],
                g["lr"] / bc1, bc2 ** 0.5, L.stream())
@@ -455,6 +469,8 @@ class HipAdam:
     def next_step_args(self):
         """Counts one optimiser step and returns its `ia_adam_args` (by reference) for an entry point that finishes
         with the reduction + Adam launch itself (`ia_airl_step_shaped`)."""
+        if self.decoupled:
+            raise NotImplementedError("the fused AIRL update steps with Adam, not AdamW")
         g = self.param_groups[0]
         self.step_count += 1
         b1, b2 = g["betas"]

@@ -512,3 +512,92 @@ class HipAdam(th.optim.Optimizer):
                                                group["eps"], group["weight_decay"], group["lr"] / (1.0 - b1 ** t),
                                                (1.0 - b2 ** t) ** 0.5)
         return loss
+
+
+# ------------------------------------------------------------------------------------ preference comparisons
+
+@th.library.custom_op("imitation_amd::preference_loss", mutates_args=(), device_types="cuda")
+def preference_loss_raw(rewards: Tensor, pair_off: Tensor, prefs: Tensor, gt_rewards: Optional[Tensor],
+                        discount_factor: float, noise_prob: float, threshold: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """`PreferenceModel.probability` + `CrossEntropyRewardLoss.forward` (`preference_comparisons.py:491-531,1048-1091`)
+    on per-row rewards of fragment pairs (`ia_pref_loss`: pair p's fragment 1 rows start at `2 * pair_off[p]`, its
+    fragment 2 rows follow). Returns `(stats[3] = (loss, accuracy, gt_reward_loss), d_rewards = d loss / d rewards,
+    probs[P])`."""
+    rewards = _dev(rewards, "rewards").reshape(-1).contiguous()
+    P = pair_off.numel() - 1
+    stats = th.empty(3, device=rewards.device)
+    d = th.empty_like(rewards)
+    probs = th.empty(P, device=rewards.device)
+    gt = gt_rewards.reshape(-1).contiguous() if gt_rewards is not None else None
+    L.call("ia_pref_loss", L.ptr(rewards), L.ptr(pair_off.contiguous()), P, L.ptr(prefs.contiguous()), L.ptr(gt),
+           float(discount_factor), float(noise_prob), float(threshold), 1.0, L.ptr(d), L.ptr(probs), None, L.ptr(stats),
+           L.stream())
+    return stats, d, probs
+
+
+@preference_loss_raw.register_fake
+def _(rewards, pair_off, prefs, gt_rewards, discount_factor, noise_prob, threshold):
+    return rewards.new_empty(3), rewards.new_empty(rewards.numel()), rewards.new_empty(pair_off.numel() - 1)
+
+
+class _PrefLoss(th.autograd.Function):
+    @staticmethod
+    def forward(ctx, rewards, pair_off, prefs, gt_rewards, discount_factor, noise_prob, threshold):
+        stats, d, probs = th.ops.imitation_amd.preference_loss(rewards, pair_off, prefs, gt_rewards, discount_factor,
+                                                               noise_prob, threshold)
+        ctx.save_for_backward(d)
+        ctx.shape = rewards.shape
+        ctx.mark_non_differentiable(stats, probs)
+        return stats[0].clone(), stats, probs
+
+    @staticmethod
+    def backward(ctx, dloss, _dstats, _dprobs):
+        (d,) = ctx.saved_tensors
+        return (d * dloss).reshape(ctx.shape), None, None, None, None, None, None
+
+
+def preference_loss(rewards: Tensor, pair_off: Tensor, prefs: Tensor, gt_rewards: Optional[Tensor] = None,
+                    discount_factor: float = 1.0, noise_prob: float = 0.0, threshold: float = 50.0):
+    """Differentiable preference cross-entropy of fragment pairs (see `preference_loss_raw`): `(loss, stats[3], probs)`;
+    the gradient flows to `rewards`."""
+    return _PrefLoss.apply(_dev(rewards, "rewards"), pair_off.to(th.int32), prefs.float(), gt_rewards,
+                           float(discount_factor), float(noise_prob), float(threshold))
+
+
+@th.library.custom_op("imitation_amd::adamw_step", mutates_args=("p", "m", "v"), device_types="cuda")
+def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, beta1: float, beta2: float, eps: float, decay: float,
+               step_size: float, bc2_sqrt: float) -> None:
+    """`torch.optim.AdamW` single-tensor step (`decay = 1 - lr * weight_decay`, see `adam_step`)."""
+    L.call("ia_adamw_step", L.ptr(p), L.ptr(_dev(g, "g")), L.ptr(m), L.ptr(v), p.numel(), beta1, beta2, eps, decay,
+           step_size, bc2_sqrt, L.stream())
+
+
+class HipAdamW(th.optim.Optimizer):
+    """`torch.optim.AdamW` (no amsgrad) over `nn.Parameter`s, one `imitation_amd::adamw_step` launch per parameter
+    tensor: what `BasicRewardTrainer` builds for an `nn.Module` reward net (`preference_comparisons.py:1214`)."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 amsgrad: bool = False):
+        if amsgrad:
+            raise NotImplementedError("amsgrad is not implemented on the HIP path")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+
+    @th.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for group in self.param_groups:
+            b1, b2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"] = 0
+                    st["exp_avg"] = th.zeros_like(p, memory_format=th.contiguous_format)
+                    st["exp_avg_sq"] = th.zeros_like(p, memory_format=th.contiguous_format)
+                st["step"] += 1
+                t = st["step"]
+                th.ops.imitation_amd.adamw_step(p.data, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"], b1, b2,
+                                                group["eps"], 1.0 - group["lr"] * group["weight_decay"],
+                                                group["lr"] / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5)
+        return loss

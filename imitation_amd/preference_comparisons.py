@@ -1,0 +1,955 @@
+"""`algorithms/preference_comparisons.py`: reward learning from preferences between trajectory fragments (the
+reference's RLHF pipeline), with the reward model trained on the device.
+
+The host side keeps the reference's constructors, defaults, errors, RNG draws and logger keys. The reward-model update
+(`BasicRewardTrainer._train`) runs on the GPU:
+
+* a product `reward_nets.BasicRewardNet` (also under `NormalizedRewardNet`): the dataset's fragments live in a device
+  table; one training call gathers each minibatch's rows by pair index, applies the input `RunningNorm` once per fragment
+  in the reference's order (`ia_pref_frag_moments` + `ia_running_norm_merge_seq` + `ia_pref_norm_apply_seq`), runs the
+  dense stack, the fused preference loss (`ia_pref_loss`), the backward and AdamW (`ia_reduce_partials_adamw` /
+  `ia_adamw_step`). No host synchronisation between minibatches; the statistics are read back once per call and
+  replayed into the logger;
+* a product `BasicShapedRewardNet` without input normalisation: its shaped forward, `ia_pref_loss` and its backward;
+* a `modules.RewardNet` (`nn.Module`): its own forward with autograd, `ops.preference_loss`, `ops.HipAdamW`.
+
+Out of scope here (each raises `NotImplementedError`): `ActiveSelectionFragmenter`, reward ensembles, regularizers and
+exploration in `AgentTrainer`.
+"""
+from __future__ import annotations
+
+import abc
+import ctypes as C
+import math
+import pickle
+import re
+from typing import Any, Callable, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch as th
+
+from imitation_amd import _lib as L
+from imitation_amd import modules, ops, reward_nets, rollout
+from imitation_amd.data_types import ExpertIndexStream, TrajectoryWithRew, Transitions, flatten_trajectories
+from imitation_amd.logger import HierarchicalLogger, configure as configure_logger
+from imitation_amd.networks import HipAdam, TransitionTable, gather_concat, training
+from imitation_amd.wrappers import BufferingWrapper, RewardVecEnvWrapper
+
+AnyRewardNet = Union[reward_nets.RewardNet, modules.RewardNet]
+
+
+# ---------------------------------------------------------------------------------------------- trajectory generators
+
+class TrajectoryGenerator(abc.ABC):
+    """`preference_comparisons.py:51-99`."""
+
+    def __init__(self, custom_logger: Optional[HierarchicalLogger] = None):
+        self.logger = custom_logger or configure_logger()
+
+    @abc.abstractmethod
+    def sample(self, steps: int) -> Sequence[TrajectoryWithRew]:
+        """Trajectories with at least `steps` transitions in total (environment rewards)."""
+
+    def train(self, steps: int, **kwargs: Any) -> None:
+        """Trains an agent if the generator has one (nothing by default)."""
+
+    @property
+    def logger(self) -> HierarchicalLogger:
+        return self._logger
+
+    @logger.setter
+    def logger(self, value: HierarchicalLogger) -> None:
+        self._logger = value
+
+
+class TrajectoryDataset(TrajectoryGenerator):
+    """`preference_comparisons.py:102-124`: a fixed dataset of trajectories, shuffled with `rng` on every `sample`."""
+
+    def __init__(self, trajectories: Sequence[TrajectoryWithRew], rng: np.random.Generator,
+                 custom_logger: Optional[HierarchicalLogger] = None):
+        super().__init__(custom_logger=custom_logger)
+        self._trajectories = trajectories
+        self.rng = rng
+
+    def sample(self, steps: int) -> Sequence[TrajectoryWithRew]:
+        trajectories = list(self._trajectories)
+        self.rng.shuffle(trajectories)
+        return _get_trajectories(trajectories, steps)
+
+
+def _check_for_correct_spaces(venv, observation_space, action_space) -> None:
+    """SB3 `utils.check_for_correct_spaces`."""
+    if observation_space != venv.observation_space:
+        raise ValueError(f"Observation spaces do not match: {observation_space} != {venv.observation_space}")
+    if action_space != venv.action_space:
+        raise ValueError(f"Action spaces do not match: {action_space} != {venv.action_space}")
+
+
+class AgentTrainer(TrajectoryGenerator):
+    """`preference_comparisons.py:127-316`: trains an RL algorithm (`imitation_amd.PPO`) on the reward model and
+    samples its trajectories. With a `RewardNet` the reward wrapper carries the net's bound `predict_processed`, so
+    `PPO.collect_rollouts` relabels whole rollouts on the device (its fused / module paths)."""
+
+    def __init__(self, algorithm, reward_fn, venv, rng: np.random.Generator, exploration_frac: float = 0.0,
+                 switch_prob: float = 0.5, random_prob: float = 0.5, custom_logger: Optional[HierarchicalLogger] = None):
+        if exploration_frac > 0:
+            raise NotImplementedError("exploration (ExplorationWrapper) is not implemented: use exploration_frac=0")
+        self.algorithm = algorithm
+        super().__init__(custom_logger)
+        if isinstance(reward_fn, (reward_nets.RewardNet, modules.RewardNet)):
+            _check_for_correct_spaces(venv, reward_fn.observation_space, reward_fn.action_space)
+            reward_fn = reward_fn.predict_processed
+        self.reward_fn = reward_fn
+        self.exploration_frac = exploration_frac
+        self.switch_prob, self.random_prob = switch_prob, random_prob
+        self.rng = rng
+        self.buffering_wrapper = BufferingWrapper(venv)
+        self.venv = self.reward_venv_wrapper = RewardVecEnvWrapper(self.buffering_wrapper, reward_fn=self.reward_fn)
+        self.log_callback = self.reward_venv_wrapper.make_log_callback()
+        self.algorithm.set_env(self.venv)
+        assert self.algorithm.get_env() is not None
+
+    def train(self, steps: int, **kwargs) -> None:
+        n_transitions = self.buffering_wrapper.n_transitions
+        if n_transitions:
+            raise RuntimeError(f"There are {n_transitions} transitions left in the buffer. "
+                               "Call AgentTrainer.sample() first to clear them.")
+        self.algorithm.learn(total_timesteps=steps, reset_num_timesteps=False, callback=self.log_callback, **kwargs)
+
+    def sample(self, steps: int) -> Sequence[TrajectoryWithRew]:
+        agent_trajs, _ = self.buffering_wrapper.pop_finished_trajectories()
+        agent_trajs = agent_trajs[::-1]
+        avail_steps = sum(len(traj) for traj in agent_trajs)
+        exploration_steps = int(self.exploration_frac * steps)
+        agent_steps = steps - exploration_steps
+        if avail_steps < agent_steps:
+            self.logger.log(f"Requested {agent_steps} transitions but only {avail_steps} in buffer. "
+                            f"Sampling {agent_steps - avail_steps} additional transitions.")
+            sample_until = rollout.make_sample_until(min_timesteps=agent_steps - avail_steps, min_episodes=None)
+            algo_venv = self.algorithm.get_env()
+            assert algo_venv is not None
+            rollout.generate_trajectories(self.algorithm, algo_venv, sample_until=sample_until,
+                                          deterministic_policy=False, rng=self.rng)
+            additional_trajs, _ = self.buffering_wrapper.pop_finished_trajectories()
+            agent_trajs = list(agent_trajs) + list(additional_trajs)
+        return list(_get_trajectories(agent_trajs, agent_steps))
+
+    @property
+    def logger(self) -> HierarchicalLogger:
+        return super().logger
+
+    @logger.setter
+    def logger(self, value: HierarchicalLogger) -> None:
+        self._logger = value
+        self.algorithm.set_logger(self.logger)
+
+
+def _get_trajectories(trajectories: Sequence[TrajectoryWithRew], steps: int) -> Sequence[TrajectoryWithRew]:
+    """`preference_comparisons.py:319-342`."""
+    if steps == 0:
+        return []
+    available_steps = sum(len(traj) for traj in trajectories)
+    if available_steps < steps:
+        raise RuntimeError(f"Asked for {steps} transitions but only {available_steps} available")
+    steps_cumsum = np.cumsum([len(traj) for traj in trajectories])
+    idx = int((steps_cumsum >= steps).argmax())
+    trajectories = trajectories[: idx + 1]
+    assert sum(len(traj) for traj in trajectories) >= steps
+    return trajectories
+
+
+# ---------------------------------------------------------------------------------------------- preference model
+
+def get_base_model(reward_model):
+    """`preference_comparisons.py:1441-1446`."""
+    base_model = reward_model
+    while hasattr(base_model, "base"):
+        base_model = base_model.base
+    return base_model
+
+
+def _is_ensemble(model) -> bool:
+    return type(model).__name__ in ("RewardEnsemble", "AddSTDRewardWrapper")
+
+
+class PreferenceModel:
+    """`preference_comparisons.py:345-531`: the Boltzmann-rational probability that fragment 1 is preferred. The
+    probabilities are computed on the device (`ia_pref_loss`)."""
+
+    def __init__(self, model: AnyRewardNet, noise_prob: float = 0.0, discount_factor: float = 1.0,
+                 threshold: float = 50) -> None:
+        self.model = model
+        self.noise_prob = noise_prob
+        self.discount_factor = discount_factor
+        self.threshold = threshold
+        if _is_ensemble(get_base_model(model)):
+            raise NotImplementedError("reward ensembles (RewardEnsemble / AddSTDRewardWrapper) are not implemented")
+        self.ensemble_model = None
+
+    def parameters(self):
+        return self.model.parameters()
+
+    def rewards(self, transitions: Transitions) -> th.Tensor:
+        """Rewards `[n]` of the model for the transitions (device tensor)."""
+        preprocessed = self.model.preprocess(transitions.obs, transitions.acts, transitions.next_obs, transitions.dones)
+        rews = self.model(*preprocessed)
+        assert rews.shape == (len(transitions.obs),)
+        return rews
+
+    def _probs(self, rews1: th.Tensor, rews2: th.Tensor) -> th.Tensor:
+        L1 = rews1.shape[0]
+        rows = th.cat([rews1.reshape(-1).float(), rews2.reshape(-1).float()]).contiguous()
+        off = th.tensor([0, L1], dtype=th.int32, device=rows.device)
+        y = th.zeros(1, device=rows.device)
+        probs = th.empty(1, device=rows.device)
+        L.call("ia_pref_loss", L.ptr(rows), L.ptr(off), 1, L.ptr(y), None, float(self.discount_factor),
+               float(self.noise_prob), float(self.threshold), 1.0, None, L.ptr(probs), None, None, L.stream())
+        return probs[0]
+
+    def probability(self, rews1: th.Tensor, rews2: th.Tensor) -> th.Tensor:
+        """`preference_comparisons.py:491-531` (a 0-dim device tensor)."""
+        assert rews1.ndim == rews2.ndim == 1
+        dev = _device_of(self.model)
+        return self._probs(th.as_tensor(rews1, device=dev), th.as_tensor(rews2, device=dev))
+
+    def __call__(self, fragment_pairs) -> Tuple[th.Tensor, Optional[th.Tensor]]:
+        return self.forward(fragment_pairs)
+
+    def forward(self, fragment_pairs) -> Tuple[th.Tensor, Optional[th.Tensor]]:
+        """`preference_comparisons.py:411-455`: `(probs, gt_probs)` of every pair (device tensors)."""
+        probs, gt_probs = [], []
+        gt_available = _trajectory_pair_includes_reward(fragment_pairs[0])
+        for frag1, frag2 in fragment_pairs:
+            rews1 = self.rewards(flatten_trajectories([frag1]))
+            rews2 = self.rewards(flatten_trajectories([frag2]))
+            probs.append(self.probability(rews1.detach(), rews2.detach()))
+            if gt_available:
+                gt_probs.append(self.probability(th.from_numpy(frag1.rews), th.from_numpy(frag2.rews)))
+        return th.stack(probs), (th.stack(gt_probs) if gt_available else None)
+
+
+def _device_of(model) -> th.device:
+    dev = model.device
+    return dev() if callable(dev) else dev
+
+
+def _trajectory_pair_includes_reward(fragment_pair) -> bool:
+    frag1, frag2 = fragment_pair
+    return isinstance(frag1, TrajectoryWithRew) and isinstance(frag2, TrajectoryWithRew)
+
+
+# ---------------------------------------------------------------------------------------------- fragmenters / gatherers
+
+class Fragmenter(abc.ABC):
+    """`preference_comparisons.py:534-561`."""
+
+    def __init__(self, custom_logger: Optional[HierarchicalLogger] = None):
+        self.logger = custom_logger or configure_logger()
+
+    @abc.abstractmethod
+    def __call__(self, trajectories: Sequence[TrajectoryWithRew], fragment_length: int, num_pairs: int):
+        """Pairs of fragments cut from `trajectories`."""
+
+
+class RandomFragmenter(Fragmenter):
+    """`preference_comparisons.py:564-666`: fragments drawn uniformly with replacement (same draws, same order)."""
+
+    def __init__(self, rng: np.random.Generator, warning_threshold: int = 10,
+                 custom_logger: Optional[HierarchicalLogger] = None) -> None:
+        super().__init__(custom_logger)
+        self.rng = rng
+        self.warning_threshold = warning_threshold
+
+    def __call__(self, trajectories, fragment_length, num_pairs):
+        fragments, self.last_picks = [], []
+        prev_num_trajectories = len(trajectories)
+        trajectories = [traj for traj in trajectories if len(traj) >= fragment_length]
+        if len(trajectories) == 0:
+            raise ValueError("No trajectories are long enough for the desired fragment length "
+                             f"of {fragment_length}.")
+        num_discarded = prev_num_trajectories - len(trajectories)
+        if num_discarded:
+            self.logger.log(f"Discarded {num_discarded} out of {prev_num_trajectories} trajectories because they are "
+                            f"shorter than the desired length of {fragment_length}.")
+        weights = [len(traj) for traj in trajectories]
+        num_transitions = 2 * num_pairs * fragment_length
+        if sum(weights) < num_transitions:
+            self.logger.warn("Fewer transitions available than needed for desired number of fragment pairs. "
+                             "Some transitions will appear multiple times.")
+        elif self.warning_threshold and sum(weights) < self.warning_threshold * num_transitions:
+            self.logger.warn(f"Samples will contain {num_transitions} transitions in total and only {sum(weights)} "
+                             "are available. Because we sample with replacement, a significant number of transitions "
+                             "are likely to appear multiple times.")
+        # `rng.choice(trajectories, p=...)` draws an index exactly like `rng.choice(len(trajectories), p=...)`
+        p = np.array(weights) / sum(weights)
+        for _ in range(2 * num_pairs):
+            k = int(self.rng.choice(len(trajectories), p=p))
+            traj = trajectories[k]
+            n = len(traj)
+            start = int(self.rng.integers(0, n - fragment_length, endpoint=True))
+            end = start + fragment_length
+            terminal = (end == n) and traj.terminal
+            fragments.append(TrajectoryWithRew(obs=traj.obs[start:end + 1], acts=traj.acts[start:end],
+                                               infos=traj.infos[start:end] if traj.infos is not None else None,
+                                               rews=traj.rews[start:end], terminal=terminal))
+            self.last_picks.append((k, start))
+        iterator = iter(fragments)
+        return list(zip(iterator, iterator))
+
+
+class ActiveSelectionFragmenter(Fragmenter):
+    """`preference_comparisons.py:669-818` (not implemented: it needs reward ensembles)."""
+
+    def __init__(self, *args, **kwargs) -> None:
+        raise NotImplementedError("ActiveSelectionFragmenter needs reward ensembles, which are not implemented")
+
+    def __call__(self, trajectories, fragment_length, num_pairs):
+        raise NotImplementedError
+
+
+class PreferenceGatherer(abc.ABC):
+    """`preference_comparisons.py:776-819`."""
+
+    def __init__(self, rng: Optional[np.random.Generator] = None,
+                 custom_logger: Optional[HierarchicalLogger] = None) -> None:
+        del rng
+        self.logger = custom_logger or configure_logger()
+
+    @abc.abstractmethod
+    def __call__(self, fragment_pairs) -> np.ndarray:
+        """Probabilities that fragment 1 is preferred, shape `(b,)`."""
+
+
+class SyntheticGatherer(PreferenceGatherer):
+    """`preference_comparisons.py:821-906`: synthetic preferences from the ground-truth rewards."""
+
+    def __init__(self, temperature: float = 1, discount_factor: float = 1, sample: bool = True,
+                 rng: Optional[np.random.Generator] = None, threshold: float = 50,
+                 custom_logger: Optional[HierarchicalLogger] = None) -> None:
+        super().__init__(custom_logger=custom_logger)
+        self.temperature = temperature
+        self.discount_factor = discount_factor
+        self.sample = sample
+        self.rng = rng
+        self.threshold = threshold
+        if self.sample and self.rng is None:
+            raise ValueError("If `sample` is True, then `rng` must be provided.")
+
+    def __call__(self, fragment_pairs) -> np.ndarray:
+        returns1, returns2 = self._reward_sums(fragment_pairs)
+        if self.temperature == 0:
+            return (np.sign(returns1 - returns2) + 1) / 2
+        returns1 /= self.temperature
+        returns2 /= self.temperature
+        returns_diff = np.clip(returns2 - returns1, -self.threshold, self.threshold)
+        model_probs = 1 / (1 + np.exp(returns_diff))
+        entropy = -(_xlogy(model_probs, model_probs) + _xlogy(1 - model_probs, 1 - model_probs)).mean()
+        self.logger.record("entropy", entropy)
+        if self.sample:
+            assert self.rng is not None
+            return self.rng.binomial(n=1, p=model_probs).astype(np.float32)
+        return model_probs
+
+    def _reward_sums(self, fragment_pairs) -> Tuple[np.ndarray, np.ndarray]:
+        rews1, rews2 = zip(*[(rollout.discounted_sum(f1.rews, self.discount_factor),
+                              rollout.discounted_sum(f2.rews, self.discount_factor)) for f1, f2 in fragment_pairs])
+        return np.array(rews1, dtype=np.float32), np.array(rews2, dtype=np.float32)
+
+
+def _xlogy(x: np.ndarray, y: np.ndarray) -> np.ndarray:
+    """`scipy.special.xlogy`: 0 where x == 0, else x * log(y)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = x * np.log(y)
+    return np.where(x == 0, 0.0, out)
+
+
+# ---------------------------------------------------------------------------------------------- dataset
+
+class PreferenceDataset:
+    """`preference_comparisons.py:909-997`: fragment pairs and preferences, a FIFO of at most `max_size` pairs.
+    The device mirror of its rows (`device_table`) is rebuilt lazily and never pickled."""
+
+    def __init__(self, max_size: Optional[int] = None) -> None:
+        self.fragments1: List[TrajectoryWithRew] = []
+        self.fragments2: List[TrajectoryWithRew] = []
+        self.max_size = max_size
+        self.preferences: np.ndarray = np.array([])
+        self._mirror = None
+
+    def push(self, fragments, preferences: np.ndarray) -> None:
+        fragments1, fragments2 = zip(*fragments)
+        if preferences.shape != (len(fragments),):
+            raise ValueError(f"Unexpected preferences shape {preferences.shape}, expected {(len(fragments),)}")
+        if preferences.dtype != np.float32:
+            raise ValueError("preferences should have dtype float32")
+        self.fragments1.extend(fragments1)
+        self.fragments2.extend(fragments2)
+        self.preferences = np.concatenate((self.preferences, preferences))
+        if self.max_size is not None:
+            extra = len(self.preferences) - self.max_size
+            if extra > 0:
+                self.fragments1 = self.fragments1[extra:]
+                self.fragments2 = self.fragments2[extra:]
+                self.preferences = self.preferences[extra:]
+        self._mirror = None
+
+    def __getitem__(self, key):
+        return (self.fragments1[key], self.fragments2[key]), self.preferences[key]
+
+    def __len__(self) -> int:
+        assert len(self.fragments1) == len(self.fragments2) == len(self.preferences)
+        return len(self.fragments1)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_mirror"] = None
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.__dict__.setdefault("_mirror", None)
+
+    def save(self, path) -> None:
+        with open(path, "wb") as file:
+            pickle.dump(self, file)
+
+    @staticmethod
+    def load(path) -> "PreferenceDataset":
+        with open(path, "rb") as file:
+            return pickle.load(file)
+
+    def device_table(self, device, discrete: bool) -> "_FragmentTable":
+        m = self._mirror
+        if m is None or m.device != th.device(device) or m.discrete != discrete:
+            m = self._mirror = _FragmentTable(self, th.device(device), discrete)
+        return m
+
+
+class _FragmentTable:
+    """The dataset's rows on the device, pair by pair: pair i's fragment 1 rows, then its fragment 2 rows."""
+
+    def __init__(self, ds: PreferenceDataset, device: th.device, discrete: bool):
+        self.device, self.discrete = device, discrete
+        n = len(ds)
+        lens = np.array([len(f) for f in ds.fragments1], dtype=np.int64)
+        if any(len(f2) != l for f2, l in zip(ds.fragments2, lens)):
+            raise ValueError("the two fragments of a pair must have the same length")
+        frags = [f for pair in zip(ds.fragments1, ds.fragments2) for f in pair]
+        tr = flatten_trajectories(frags)
+        self.pair_len = lens
+        self.pair_start = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(2 * lens, out=self.pair_start[1:])
+        obs = th.as_tensor(np.asarray(tr.obs, np.float32).reshape(len(tr.obs), -1)).to(device)
+        nxt = th.as_tensor(np.asarray(tr.next_obs, np.float32).reshape(len(tr.obs), -1)).to(device)
+        if discrete:
+            acts = th.as_tensor(np.asarray(tr.acts, np.int64).reshape(-1)).to(device)
+        else:
+            acts = th.as_tensor(np.asarray(tr.acts, np.float32).reshape(len(tr.obs), -1)).to(device)
+        dones = th.as_tensor(np.asarray(tr.dones, np.uint8)).to(device)
+        self.table = TransitionTable(obs.contiguous(), acts.contiguous(), nxt.contiguous(), dones.contiguous(), discrete)
+        self.gt = th.as_tensor(np.asarray(tr.rews, np.float32)).to(device)
+        self.prefs = np.asarray(ds.preferences, np.float32)
+        self.has_gt = bool(n) and _trajectory_pair_includes_reward(ds[0][0])
+
+    def batch(self, pairs: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(row indices in batch order, pair offsets [P+1] in steps) of the pairs `pairs`."""
+        lens = self.pair_len[pairs]
+        off = np.zeros(len(pairs) + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        rows = np.concatenate([np.arange(self.pair_start[p], self.pair_start[p] + 2 * l) for p, l in zip(pairs, lens)])
+        return rows, off
+
+
+# ---------------------------------------------------------------------------------------------- losses
+
+class LossAndMetrics(NamedTuple):
+    """`preference_comparisons.py:1000-1004`."""
+    loss: th.Tensor
+    metrics: Mapping[str, th.Tensor]
+
+
+class RewardLoss(abc.ABC):
+    """`preference_comparisons.py:1006-1028`."""
+
+    @abc.abstractmethod
+    def forward(self, fragment_pairs, preferences: np.ndarray, preference_model: PreferenceModel) -> LossAndMetrics:
+        """Loss and metrics of a batch."""
+
+    def __call__(self, *args, **kwargs):
+        return self.forward(*args, **kwargs)
+
+
+class CrossEntropyRewardLoss(RewardLoss):
+    """`preference_comparisons.py:1037-1091`: cross entropy of the model's preference probabilities; metrics
+    `accuracy` and (with ground-truth rewards) `gt_reward_loss`."""
+
+    def forward(self, fragment_pairs, preferences, preference_model: PreferenceModel) -> LossAndMetrics:
+        ds = PreferenceDataset()
+        ds.push(fragment_pairs, np.asarray(preferences, dtype=np.float32))
+        loss, stats = _PairBatchRunner(preference_model).loss(ds, np.arange(len(ds)))
+        metrics = {"accuracy": stats[1].detach().cpu()}
+        if _trajectory_pair_includes_reward(fragment_pairs[0]):
+            metrics["gt_reward_loss"] = stats[2].detach().cpu()
+        return LossAndMetrics(loss=loss, metrics=metrics)
+
+
+# ---------------------------------------------------------------------------------------------- reward trainers
+
+def loader_epoch_permutations(n: int, epochs: int) -> List[np.ndarray]:
+    """The sample orders of `epochs` passes over `DataLoader(range(n), shuffle=True)` (single process), drawn from
+    torch's global CPU generator as the loader draws them: per epoch the iterator's base seed, then the sampler's seed
+    and `randperm(n)` (the helpers behind `data_types.ExpertIndexStream`)."""
+    out = []
+    for _ in range(epochs):
+        ExpertIndexStream._draw_int64()                       # iter(loader): base seed
+        seed = ExpertIndexStream._draw_int64()                # first next(): the sampler's generator seed
+        g = th.Generator()
+        g.manual_seed(seed)
+        out.append(th.randperm(n, generator=g).numpy())
+    return out
+
+
+class RewardTrainer(abc.ABC):
+    """`preference_comparisons.py:1094-1136`."""
+
+    def __init__(self, preference_model: PreferenceModel, custom_logger: Optional[HierarchicalLogger] = None) -> None:
+        self._preference_model = preference_model
+        self._logger = custom_logger or configure_logger()
+
+    @property
+    def logger(self) -> HierarchicalLogger:
+        return self._logger
+
+    @logger.setter
+    def logger(self, custom_logger: HierarchicalLogger) -> None:
+        self._logger = custom_logger
+
+    def train(self, dataset: PreferenceDataset, epoch_multiplier: float = 1.0) -> None:
+        with training(self._preference_model.model):
+            self._train(dataset, epoch_multiplier)
+
+    @abc.abstractmethod
+    def _train(self, dataset: PreferenceDataset, epoch_multiplier: float) -> None:
+        """Trains the reward model."""
+
+
+class BasicRewardTrainer(RewardTrainer):
+    """`preference_comparisons.py:1139-1324` on the device. The whole `train` call is enqueued at once: the pair order
+    of every epoch is drawn first, each minibatch's statistics row (loss, accuracy, gt_reward_loss) stays on the device,
+    and the rows are read back once and replayed into the logger in the reference's order."""
+
+    def __init__(self, preference_model: PreferenceModel, loss: RewardLoss, rng: np.random.Generator,
+                 batch_size: int = 32, minibatch_size: Optional[int] = None, epochs: int = 1, lr: float = 1e-3,
+                 custom_logger: Optional[HierarchicalLogger] = None, regularizer_factory=None) -> None:
+        super().__init__(preference_model, custom_logger)
+        if regularizer_factory is not None:
+            raise NotImplementedError("reward regularizers are not implemented")
+        if not isinstance(loss, CrossEntropyRewardLoss):
+            raise NotImplementedError("only CrossEntropyRewardLoss is implemented on the device")
+        self.loss = loss
+        self.batch_size = batch_size
+        self.minibatch_size = minibatch_size or batch_size
+        if self.batch_size % self.minibatch_size != 0:
+            raise ValueError("Batch size must be a multiple of minibatch size.")
+        self.epochs = epochs
+        self.rng = rng
+        self.regularizer = None
+        self._runner = _PairBatchRunner(preference_model)
+        self.optim = self._runner.make_optimizer(lr)
+        self.host_stepped = False   # tests: one host round trip per minibatch (the same launches)
+
+    @property
+    def requires_regularizer_update(self) -> bool:
+        return False
+
+    def _schedule(self, n: int, epochs: int):
+        """[(epoch, pairs of the minibatch, loss scale, accumulate, step after it)] of `epochs` passes."""
+        out = []
+        for epoch, perm in enumerate(loader_epoch_permutations(n, epochs)):
+            acc = 0
+            for s in range(0, n, self.minibatch_size):
+                mb = perm[s:s + self.minibatch_size]
+                first = acc == 0
+                acc += len(mb)
+                step = acc >= self.batch_size or s + self.minibatch_size >= n
+                out.append((epoch, mb, len(mb) / self.batch_size, not first, step))
+                if acc >= self.batch_size:
+                    acc = 0
+        return out
+
+    def _train(self, dataset: PreferenceDataset, epoch_multiplier: float = 1.0) -> None:
+        epochs = round(self.epochs * epoch_multiplier)
+        assert epochs > 0, "Must train for at least one epoch."
+        sched = self._schedule(len(dataset), epochs)
+        stats = self._runner.run(dataset, sched, self.optim, host_stepped=self.host_stepped)
+        gt = self._runner.has_gt
+        epoch_num = epochs - 1
+        with self.logger.accumulate_means("reward"):
+            for (epoch, _, _, _, _), row in zip(sched, stats):
+                with self.logger.add_key_prefix(f"epoch-{epoch}"):
+                    with self.logger.add_key_prefix("train"):
+                        self.logger.record("loss", float(row[0]))
+                        self.logger.record("accuracy", float(row[1]))
+                        if gt:
+                            self.logger.record("gt_reward_loss", float(row[2]))
+        keys = list(self.logger.name_to_value.keys())
+        outer_prefix = self.logger.get_accumulate_prefixes()
+        for key in keys:
+            base_path = f"{outer_prefix}reward/"
+            epoch_path = f"mean/{base_path}epoch-{epoch_num}/"
+            final_path = f"{base_path}final/"
+            regex_match = re.match(rf"{epoch_path}(.+)", key)
+            if regex_match:
+                (key_name,) = regex_match.groups()
+                self.logger.record(f"{final_path}{key_name}", self.logger.name_to_value[key])
+
+
+def _as_basic(model):
+    """The product `BasicRewardNet` whose forward `model`'s forward is (through `PredictProcessedWrapper`s), or None."""
+    m = model
+    while isinstance(m, reward_nets.PredictProcessedWrapper):
+        m = m.base
+    return m if type(m) is reward_nets.BasicRewardNet else None
+
+
+class _PairBatchRunner:
+    """Forward, loss, backward and optimiser steps of minibatches of fragment pairs; the path is chosen from the net's
+    type: "basic" (product `BasicRewardNet`), "shaped" (product `ShapedRewardNet`) or "module" (`nn.Module`)."""
+
+    def __init__(self, pm: PreferenceModel):
+        self.pm = pm
+        model = pm.model
+        self.basic = _as_basic(model) if isinstance(model, reward_nets.RewardNet) else None
+        if isinstance(model, modules.RewardNet):
+            self.kind = "module"
+        elif self.basic is not None:
+            self.kind = "basic"
+        elif isinstance(model, reward_nets.ShapedRewardNet):
+            self.kind = "shaped"
+        else:
+            raise NotImplementedError(f"reward net {type(model).__name__} cannot be trained on preferences here")
+        self.has_gt = False
+
+    @property
+    def device(self) -> th.device:
+        return _device_of(self.pm.model)
+
+    def make_optimizer(self, lr: float):
+        model = self.pm.model
+        if self.kind == "module":
+            return ops.HipAdamW(model.parameters(), lr=lr)
+        store = model._store   # (wrappers share their base's store)
+        return HipAdam(store.flat, store.grad, lr=lr, weight_decay=0.01, decoupled=True)
+
+    def _discrete(self) -> bool:
+        from imitation_amd import spaces
+        return isinstance(self.pm.model.action_space, spaces.Discrete)
+
+    # -- one minibatch's loss on the device: (loss tensor for autograd or None, stats[3] device view)
+    def loss(self, ds: PreferenceDataset, pairs: np.ndarray):
+        tab = ds.device_table(self.device, self._discrete())
+        rows, off = tab.batch(pairs)
+        rows_d = th.as_tensor(rows).to(self.device)
+        off_d = th.as_tensor(off.astype(np.int32)).to(self.device)
+        y = th.as_tensor(tab.prefs[pairs]).to(self.device)
+        st = th.empty(3, device=self.device)
+        if self.kind == "module":
+            rew = self._module_rewards(tab, rows_d, off)
+            loss, stats, _ = ops.preference_loss(rew, off_d, y, tab.gt[rows_d] if tab.has_gt else None,
+                                                 self.pm.discount_factor, self.pm.noise_prob, self.pm.threshold)
+            return loss, stats
+        rew = self._product_forward(tab, rows_d, off)
+        self._launch_loss(rew, off_d, y, tab.gt[rows_d] if tab.has_gt else None, 1.0, None, st)
+        return st[0], st
+
+    def _launch_loss(self, rew, off_d, y, gt, scale, d, stats):
+        pm = self.pm
+        L.call("ia_pref_loss", L.ptr(rew), L.ptr(off_d), off_d.numel() - 1, L.ptr(y), L.ptr(gt),
+               float(pm.discount_factor), float(pm.noise_prob), float(pm.threshold), float(scale), L.ptr(d), None,
+               None, L.ptr(stats), L.stream())
+
+    def _module_rewards(self, tab: _FragmentTable, rows_d: th.Tensor, off: np.ndarray) -> th.Tensor:
+        """The module net's rewards of the rows, one call per fragment like `PreferenceModel.rewards` when the net holds a
+        normalisation layer (its statistics move per call), else one call for all rows."""
+        model = self.pm.model
+        t = tab.table
+        acts = t.acts[rows_d]
+        s, a, ns, d = model.preprocess(t.obs[rows_d], acts, t.next_obs[rows_d], t.dones[rows_d].bool())
+        if not any(isinstance(m, modules.RunningNorm) for m in model.modules()):
+            return model(s, a, ns, d).reshape(-1)
+        out, r = [], 0
+        for p in range(len(off) - 1):
+            Lp = int(off[p + 1] - off[p])
+            for _ in range(2):
+                out.append(model(s[r:r + Lp], a[r:r + Lp], ns[r:r + Lp], d[r:r + Lp]).reshape(-1))
+                r += Lp
+        return th.cat(out)
+
+    def _product_forward(self, tab: _FragmentTable, rows_d: th.Tensor, off: np.ndarray) -> th.Tensor:
+        R = int(rows_d.numel())
+        model = self.pm.model
+        if self.kind == "shaped":
+            for st in (model._base.mlp, model.potential._potential_net):
+                if st.norm is not None and st.training:
+                    raise NotImplementedError("a shaped reward net with an input RunningNorm is not implemented here")
+            self._shaped_R = R
+            return model._shaped([(tab.table, rows_d, R)], "pref", True, None)
+        net = self.basic
+        mlp = net.mlp
+        ws = mlp.train_workspace(R, "pref")
+        gather_concat(tab.table, rows_d, R, net.obs_dim, net.act_dim, net.flags, ws["X"], mlp.ldx, 0)
+        x = ws["X"]
+        nrm = mlp.norm
+        if nrm is not None:
+            D = mlp.dims[0]
+            if mlp.training:
+                lens = np.diff(off)
+                if not nrm.is_chan:
+                    raise NotImplementedError("EMANorm input layers are not implemented for preference training")
+                if len(lens) and (lens != lens[0]).any():
+                    raise NotImplementedError("an input RunningNorm with fragments of different lengths")
+                Lf, nf = int(lens[0]), 2 * len(lens)
+                need = int(L.load().ia_running_norm_ws_floats(Lf, D))
+                key = ("pref_rn", nf, Lf)
+                rw = mlp._ws.get(key)
+                if rw is None:
+                    rw = mlp._ws[key] = {"m": th.empty(nf, need, device=x.device),
+                                         "snap": th.empty(nf, 2, D, device=x.device)}
+                L.call("ia_pref_frag_moments", L.ptr(x), mlp.ldx, nf, Lf, D, need, L.ptr(rw["m"]), L.stream())
+                L.call("ia_running_norm_merge_seq", L.ptr(rw["m"]), nf, need, 1, Lf, D, D, L.ptr(nrm.running_mean),
+                       L.ptr(nrm.running_var), L.ptr(nrm.count), L.ptr(rw["snap"]), L.stream())
+                L.call("ia_pref_norm_apply_seq", L.ptr(x), mlp.ldx, nf, Lf, D, L.ptr(rw["snap"]), nrm.eps,
+                       L.ptr(ws["Xn"]), mlp.ldx, L.stream())
+            else:
+                nrm.apply(x, ws["Xn"], mlp.ldx, mlp.ldx, R)
+            x = ws["Xn"]
+        ws["_in"] = x
+        L.call("ia_mlp_forward", C.byref(mlp.desc), L.ptr(mlp.flat), L.ptr(x), mlp.ldx, R, L.ptr(ws["hidden"]),
+               L.ptr(ws["out"]), L.ACT_NONE, L.stream())
+        self._ws, self._R = ws, R
+        return ws["out"].reshape(R)
+
+    def _product_backward(self, d: th.Tensor, accumulate: bool, adam) -> None:
+        """Gradient of the last forward (accumulated or not); with `adam` the step is fused into the reduction."""
+        if self.kind == "shaped":
+            self.pm.model.disc_backward(d, accumulate)
+            if adam is not None:
+                adam.step()
+            return
+        mlp = self.basic.mlp
+        fuse = adam is not None and not accumulate and adam.flat.numel() == mlp.n_params
+        mlp.backward_rows(self._ws, self._R, d, accumulate, adam=adam if fuse else None)
+        if adam is not None and not fuse:
+            adam.step()
+
+    # -- a whole train call
+    def run(self, ds: PreferenceDataset, sched, optim, host_stepped: bool = False) -> np.ndarray:
+        dev = self.device
+        tab = ds.device_table(dev, self._discrete())
+        self.has_gt = tab.has_gt
+        n_mb = len(sched)
+        # every minibatch's rows, pair offsets and preferences in one upload
+        parts = [tab.batch(mb) for _, mb, _, _, _ in sched]
+        row_at = np.zeros(n_mb + 1, dtype=np.int64)
+        np.cumsum([len(r) for r, _ in parts], out=row_at[1:])
+        off_at = np.zeros(n_mb + 1, dtype=np.int64)
+        np.cumsum([len(o) for _, o in parts], out=off_at[1:])
+        rows_all = th.as_tensor(np.concatenate([r for r, _ in parts])).to(dev)
+        off_all = th.as_tensor(np.concatenate([o for _, o in parts]).astype(np.int32)).to(dev)
+        pair_at = np.zeros(n_mb + 1, dtype=np.int64)
+        np.cumsum([len(mb) for _, mb, _, _, _ in sched], out=pair_at[1:])
+        y_all = th.as_tensor(np.concatenate([tab.prefs[mb] for _, mb, _, _, _ in sched])).to(dev)
+        gt_all = tab.gt[rows_all] if tab.has_gt else None
+        stats = th.zeros(n_mb, 3, device=dev)
+        d_all = th.empty(int(row_at[-1]), device=dev)
+        for k, (_, mb, scale, accumulate, step) in enumerate(sched):
+            r0, r1 = int(row_at[k]), int(row_at[k + 1])
+            rows_d = rows_all[r0:r1]
+            off_d = off_all[int(off_at[k]):int(off_at[k + 1])]
+            y = y_all[int(pair_at[k]):int(pair_at[k + 1])]
+            gt = gt_all[r0:r1] if gt_all is not None else None
+            off = parts[k][1]
+            if self.kind == "module":
+                if not accumulate:
+                    optim.zero_grad()
+                rew = self._module_rewards(tab, rows_d, off)
+                loss, st, _ = ops.preference_loss(rew, off_d, y, gt, self.pm.discount_factor, self.pm.noise_prob,
+                                                  self.pm.threshold)
+                stats[k].copy_(st)
+                (loss * scale).backward()
+                if step:
+                    optim.step()
+            else:
+                rew = self._product_forward(tab, rows_d, off)
+                d = d_all[r0:r1]
+                self._launch_loss(rew, off_d, y, gt, scale, d, stats[k])
+                self._product_backward(d, accumulate, optim if step else None)
+            if host_stepped:
+                th.cuda.current_stream().synchronize()
+        return stats.cpu().numpy()
+
+
+def _make_reward_trainer(preference_model: PreferenceModel, loss: RewardLoss, rng: np.random.Generator,
+                         reward_trainer_kwargs: Optional[Mapping[str, Any]] = None) -> RewardTrainer:
+    """`preference_comparisons.py:1449-1472`."""
+    return BasicRewardTrainer(preference_model, loss=loss, rng=rng, **(reward_trainer_kwargs or {}))
+
+
+# ---------------------------------------------------------------------------------------------- the algorithm
+
+QUERY_SCHEDULES: Dict[str, Callable[[float], float]] = {
+    "constant": lambda t: 1.0,
+    "hyperbolic": lambda t: 1.0 / (1.0 + t),
+    "inverse_quadratic": lambda t: 1.0 / (1.0 + t**2),
+}
+
+
+def oric(x: np.ndarray) -> np.ndarray:
+    """`util/util.py:44-68`: optimal rounding under integer constraints (keeps the sum)."""
+    rounded = np.floor(x)
+    shortfall = x - rounded
+    total_shortfall = np.round(shortfall.sum()).astype(int)
+    indices = np.argsort(-shortfall)
+    rounded[indices[:total_shortfall]] += 1
+    return rounded.astype(int)
+
+
+class PreferenceComparisons:
+    """`preference_comparisons.py:1482-1753`: alternately gathers preferences on fragments of the generator's
+    trajectories, trains the reward model on them, and trains the agent on the reward model."""
+
+    def __init__(self, trajectory_generator: TrajectoryGenerator, reward_model: AnyRewardNet, num_iterations: int,
+                 fragmenter: Optional[Fragmenter] = None, preference_gatherer: Optional[PreferenceGatherer] = None,
+                 reward_trainer: Optional[RewardTrainer] = None, comparison_queue_size: Optional[int] = None,
+                 fragment_length: int = 100, transition_oversampling: float = 1, initial_comparison_frac: float = 0.1,
+                 initial_epoch_multiplier: float = 200.0, custom_logger: Optional[HierarchicalLogger] = None,
+                 allow_variable_horizon: bool = False, rng: Optional[np.random.Generator] = None,
+                 query_schedule: Union[str, Callable[[float], float]] = "hyperbolic") -> None:
+        self._logger = custom_logger or configure_logger()
+        self.allow_variable_horizon = allow_variable_horizon
+        self._horizon = None
+        self._iteration = 0
+        self.model = reward_model
+        self.rng = rng
+        has_any_rng_args_none = None in (preference_gatherer, fragmenter, reward_trainer)
+        if self.rng is None and has_any_rng_args_none:
+            raise ValueError("If you don't provide a random state, you must provide your own seeded fragmenter, "
+                             "preference gatherer, and reward_trainer. You can initialize a random state with "
+                             "`np.random.default_rng(seed)`.")
+        elif self.rng is not None and not has_any_rng_args_none:
+            raise ValueError("If you provide your own fragmenter, preference gatherer, and reward trainer, you don't "
+                             "need to provide a random state.")
+        if reward_trainer is None:
+            assert self.rng is not None
+            self.reward_trainer = _make_reward_trainer(PreferenceModel(reward_model), CrossEntropyRewardLoss(),
+                                                       rng=self.rng)
+        else:
+            self.reward_trainer = reward_trainer
+        self.reward_trainer.logger = self.logger
+        self.trajectory_generator = trajectory_generator
+        self.trajectory_generator.logger = self.logger
+        if fragmenter:
+            self.fragmenter = fragmenter
+        else:
+            assert self.rng is not None
+            self.fragmenter = RandomFragmenter(custom_logger=self.logger, rng=self.rng)
+        self.fragmenter.logger = self.logger
+        if preference_gatherer:
+            self.preference_gatherer = preference_gatherer
+        else:
+            assert self.rng is not None
+            self.preference_gatherer = SyntheticGatherer(custom_logger=self.logger, rng=self.rng)
+        self.preference_gatherer.logger = self.logger
+        self.fragment_length = fragment_length
+        self.initial_comparison_frac = initial_comparison_frac
+        self.initial_epoch_multiplier = initial_epoch_multiplier
+        self.num_iterations = num_iterations
+        self.transition_oversampling = transition_oversampling
+        if callable(query_schedule):
+            self.query_schedule = query_schedule
+        elif query_schedule in QUERY_SCHEDULES:
+            self.query_schedule = QUERY_SCHEDULES[query_schedule]
+        else:
+            raise ValueError(f"Unknown query schedule: {query_schedule}")
+        self.dataset = PreferenceDataset(max_size=comparison_queue_size)
+
+    @property
+    def logger(self) -> HierarchicalLogger:
+        return self._logger
+
+    @logger.setter
+    def logger(self, value: HierarchicalLogger) -> None:
+        self._logger = value
+
+    def _check_fixed_horizon(self, horizons) -> None:
+        """`algorithms/base.py:77-110`."""
+        if self.allow_variable_horizon:
+            return
+        hs = set(int(h) for h in horizons)
+        if self._horizon is not None:
+            hs.add(self._horizon)
+        if len(hs) > 1:
+            raise ValueError(f"Episodes of different length detected: {hs}. Variable horizon environments are "
+                             "discouraged -- termination conditions leak information about reward. If you are SURE "
+                             "you want to run imitation on a variable horizon task, then please pass in the flag: "
+                             "`allow_variable_horizon=True`.")
+        if len(hs) == 1:
+            self._horizon = hs.pop()
+
+    def query_schedule_for(self, total_comparisons: int) -> List[int]:
+        """The number of comparisons gathered at each iteration of `train(..., total_comparisons)`."""
+        initial_comparisons = int(total_comparisons * self.initial_comparison_frac)
+        total_comparisons -= initial_comparisons
+        vec_schedule = np.vectorize(self.query_schedule)
+        unnormalized_probs = vec_schedule(np.linspace(0, 1, self.num_iterations))
+        probs = unnormalized_probs / np.sum(unnormalized_probs)
+        shares = oric(probs * total_comparisons)
+        return [initial_comparisons] + shares.tolist()
+
+    def train(self, total_timesteps: int, total_comparisons: int,
+              callback: Optional[Callable[[int], None]] = None) -> Mapping[str, Any]:
+        schedule = self.query_schedule_for(total_comparisons)
+        print(f"Query schedule: {schedule}")
+        timesteps_per_iteration, extra_timesteps = divmod(total_timesteps, self.num_iterations)
+        reward_loss = None
+        reward_accuracy = None
+        for i, num_pairs in enumerate(schedule):
+            num_steps = math.ceil(self.transition_oversampling * 2 * num_pairs * self.fragment_length)
+            self.logger.log(f"Collecting {2 * num_pairs} fragments ({num_steps} transitions)")
+            trajectories = self.trajectory_generator.sample(num_steps)
+            horizons = (len(traj) for traj in trajectories if traj.terminal)
+            self._check_fixed_horizon(horizons)
+            self.logger.log("Creating fragment pairs")
+            fragments = self.fragmenter(trajectories, self.fragment_length, num_pairs)
+            with self.logger.accumulate_means("preferences"):
+                self.logger.log("Gathering preferences")
+                preferences = self.preference_gatherer(fragments)
+            self.dataset.push(fragments, preferences)
+            self.logger.log(f"Dataset now contains {len(self.dataset)} comparisons")
+            epoch_multiplier = 1.0
+            if i == 0:
+                epoch_multiplier = self.initial_epoch_multiplier
+            self.reward_trainer.train(self.dataset, epoch_multiplier=epoch_multiplier)
+            base_key = self.logger.get_accumulate_prefixes() + "reward/final/train"
+            assert f"{base_key}/loss" in self.logger.name_to_value
+            assert f"{base_key}/accuracy" in self.logger.name_to_value
+            reward_loss = self.logger.name_to_value[f"{base_key}/loss"]
+            reward_accuracy = self.logger.name_to_value[f"{base_key}/accuracy"]
+            num_steps = timesteps_per_iteration
+            if i == self.num_iterations - 1:
+                num_steps += extra_timesteps
+            with self.logger.accumulate_means("agent"):
+                self.logger.log(f"Training agent for {num_steps} timesteps")
+                self.trajectory_generator.train(steps=num_steps)
+            self.logger.dump(self._iteration)
+            if callback:
+                callback(self._iteration)
+            self._iteration += 1
+        return {"reward_loss": reward_loss, "reward_accuracy": reward_accuracy}
+
+
+class EnsembleTrainer(BasicRewardTrainer):
+    """`preference_comparisons.py:1327-1438` (not implemented)."""
+
+    def __init__(self, *args, **kwargs) -> None:
+        raise NotImplementedError("reward ensembles (EnsembleTrainer) are not implemented")

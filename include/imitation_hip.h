@@ -797,6 +797,35 @@ int ia_kde_log_density(int kernel, double h, int d, const float* Y, int ldy, con
                        const double* scale, const int* perm, const int* tiles, int n_tiles, float* partials, float* out,
                        int stages, void* stream);
 
+/* Reward-model training on preference comparisons (algorithms/preference_comparisons.py).
+ * ia_pref_loss: PreferenceModel.probability (:491-531) + CrossEntropyRewardLoss.forward (:1048-1091) of n_pairs fragment
+ * pairs on per-row rewards, forward and backward in ONE launch. Pair p has L_p = pair_off[p+1] - pair_off[p] steps (int32
+ * CSR, pair_off[0] = 0); its fragment 1 rows are rewards[2*pair_off[p] + t], its fragment 2 rows follow at + L_p.
+ *   diff = sum_t g^t (r2 - r1) (a plain sum when g == 1), clipped to +-threshold; p = noise/2 + (1 - noise) / (1 + exp(diff));
+ *   loss = mean torch binary_cross_entropy(p, prefs) (log clamp at -100), accuracy = mean((p > 0.5) == (prefs > 0.5)).
+ * gt_rewards (nullable, same layout): the same probability on the ground-truth rewards and its loss (gt_reward_loss).
+ * d_rewards (nullable, same layout) <- d(loss_scale * loss) / d rewards, torch's backward (p - y) / max(p (1 - p), 1e-12) and
+ * a zero gradient where the clip is active. probs / gt_probs (nullable) [n_pairs] <- p. stats (nullable) [3] <- (loss,
+ * accuracy, gt_reward_loss; 0 without gt_rewards). */
+int ia_pref_loss(const float* rewards, const int* pair_off, int n_pairs, const float* prefs, const float* gt_rewards,
+                 float discount_factor, float noise_prob, float threshold, float loss_scale, float* d_rewards,
+                 float* probs, float* gt_probs, float* stats, void* stream);
+/* RunningNorm updated once per fragment, in fragment order (util/networks.py:79-91 under PreferenceModel.rewards): slab
+ * moments of fragment f = rows [f*L, f*L+L) of X[., ldx] -> ws + f*ws_stride in ia_running_norm_partial's layout (feed
+ * ia_running_norm_merge_seq with rows_per_group = L), ws_stride >= ia_running_norm_ws_floats(L, D). */
+int ia_pref_frag_moments(const float* X, int ldx, int n_frags, int L, int D, int64_t ws_stride, float* ws, void* stream);
+/* ia_running_norm_apply with fragment f's own statistics: snapshots [n_frags][2][D] (ia_running_norm_merge_seq's). */
+int ia_pref_norm_apply_seq(const float* X, int ldx, int n_frags, int L, int D, const float* snapshots, float eps,
+                           float* Y, int ldy, void* stream);
+/* torch.optim.AdamW step (decoupled weight decay): params *= decay (= 1 - lr * weight_decay), then ia_adam_step's update
+ * with weight_decay = 0. ia_reduce_partials_adamw: grads = scale * sum of the slabs (ia_reduce_partials, accumulate = 0),
+ * then the same step -- one launch. */
+int ia_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
+                  float beta2, float eps, float decay, float step_size, float bc2_sqrt, void* stream);
+int ia_reduce_partials_adamw(const float* partials, int splits, int64_t n, float scale, float* grads, float* params,
+                             float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, float decay,
+                             float step_size, float bc2_sqrt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

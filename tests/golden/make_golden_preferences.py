@@ -1,0 +1,188 @@
+"""Generates `tests/golden/preference_*.npz` by running the REFERENCE's own `preference_comparisons`
+(`imitation.algorithms.preference_comparisons`, imported unmodified under `oracle.ref_shim`) with a `TrajectoryDataset`
+generator over fixed trajectories. Runs only where the reference sources are present.
+Usage: `python tests/golden/make_golden_preferences.py`.
+
+The shim has no `stable_baselines3.common.type_aliases` and its SB3 `Logger` has no `warn`, which the module touches:
+this script adds both in its own process. Each file holds the trajectories, the case's settings, the query schedule,
+the fragment picks (trajectory, start) and preferences of every iteration, the reward net's parameters and statistics
+and the AdamW state after every reward-training call, the logger's records at every dump and the returned dict.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+from imitation_amd import spaces as sp  # noqa: E402
+from oracle import ref_shim  # noqa: E402
+
+CASES = {
+    # name: settings (see run_case)
+    "preference_basic_rn": dict(obs_dim=17, act_dim=6, discrete=False, norm=True, wrap=False, n_traj=12, horizon=40,
+                                frag=10, iters=2, comparisons=24, batch=8, mb=None, epochs=2, init_mult=3.0,
+                                gamma=1.0, noise=0.0, queue=None, seed=0),
+    "preference_plain_disc_noise_accum": dict(obs_dim=7, act_dim=3, discrete=False, norm=False, wrap=False, n_traj=10,
+                                              horizon=30, frag=5, iters=3, comparisons=30, batch=8, mb=4, epochs=2,
+                                              init_mult=2.0, gamma=0.9, noise=0.1, queue=None, seed=1),
+    "preference_normalized_queue": dict(obs_dim=5, act_dim=2, discrete=False, norm=True, wrap=True, n_traj=10, horizon=25,
+                                        frag=5, iters=3, comparisons=40, batch=6, mb=3, epochs=1, init_mult=2.0,
+                                        gamma=1.0, noise=0.0, queue=14, seed=2),
+    "preference_discrete": dict(obs_dim=4, act_dim=3, discrete=True, norm=True, wrap=False, n_traj=10, horizon=30,
+                                frag=6, iters=2, comparisons=20, batch=8, mb=None, epochs=2, init_mult=2.0,
+                                gamma=0.99, noise=0.0, queue=None, seed=3),
+}
+
+
+def make_trajectories(cfg):
+    """Fixed trajectories: observations, actions and rewards drawn from their own generator (rewards correlate with the
+    first observation column, so the preferences carry signal)."""
+    r = np.random.default_rng(1000 + cfg["seed"])
+    out = []
+    for _ in range(cfg["n_traj"]):
+        T = cfg["horizon"]
+        obs = r.normal(size=(T + 1, cfg["obs_dim"])).astype(np.float32)
+        if cfg["discrete"]:
+            acts = r.integers(cfg["act_dim"], size=T).astype(np.int64)
+        else:
+            acts = r.uniform(-1, 1, size=(T, cfg["act_dim"])).astype(np.float32)
+        rews = (obs[:-1, 0] + 0.3 * r.normal(size=T)).astype(np.float32)
+        out.append((obs, acts, rews))
+    return out
+
+
+def install():
+    ref_shim.install()
+    import types as _types
+
+    from oracle import sb3_restated as sb
+    ta = _types.ModuleType("stable_baselines3.common.type_aliases")
+    ta.Schedule = object
+    sys.modules["stable_baselines3.common.type_aliases"] = ta
+    sys.modules["stable_baselines3.common"].type_aliases = ta
+    sb.Logger.warn = lambda self, *args, **kwargs: None
+    from imitation.algorithms import preference_comparisons as pc
+    from imitation.data import types
+    from imitation.rewards import reward_nets
+    from imitation.util import logger as imit_logger
+    from imitation.util import networks
+    return pc, types, reward_nets, networks, imit_logger
+
+
+def run_case(name, cfg, pc, types, reward_nets, networks, imit_logger, tmp):
+    import torch as th
+
+    raw = make_trajectories(cfg)
+    trajs = [types.TrajectoryWithRew(obs=o, acts=a, rews=w, infos=None, terminal=True) for o, a, w in raw]
+    obs_space = sp.Box(-np.inf, np.inf, (cfg["obs_dim"],), np.float32)
+    act_space = sp.Discrete(cfg["act_dim"]) if cfg["discrete"] else sp.Box(-1.0, 1.0, (cfg["act_dim"],), np.float32)
+    th.manual_seed(cfg["seed"])
+    kw = dict(normalize_input_layer=networks.RunningNorm) if cfg["norm"] else {}
+    net = reward_nets.BasicRewardNet(obs_space, act_space, **kw)
+    model = reward_nets.NormalizedRewardNet(net, networks.RunningNorm) if cfg["wrap"] else net
+    rng = np.random.default_rng(cfg["seed"])
+    logger = imit_logger.configure(os.path.join(tmp, name), ["log"])
+    gen = pc.TrajectoryDataset(trajs, rng=rng, custom_logger=logger)
+    pm = pc.PreferenceModel(model, noise_prob=cfg["noise"], discount_factor=cfg["gamma"])
+    trainer = pc.BasicRewardTrainer(pm, pc.CrossEntropyRewardLoss(), rng=rng, batch_size=cfg["batch"],
+                                    minibatch_size=cfg["mb"], epochs=cfg["epochs"], custom_logger=logger)
+    fragmenter = pc.RandomFragmenter(rng=rng, custom_logger=logger)   # its picks are recovered from the fragments
+    gatherer = pc.SyntheticGatherer(rng=rng, discount_factor=cfg["gamma"], custom_logger=logger)
+
+    rec = {"picks": [], "gathered": [], "params": [], "adam": [], "dumps": []}
+    by_id = {id(t.obs): k for k, t in enumerate(trajs)}
+
+    orig_frag = fragmenter.__call__
+
+    def frag_call(trajectories, fragment_length, num_pairs):
+        pairs = orig_frag(trajectories, fragment_length, num_pairs)
+        picks = []
+        for f in (f for p in pairs for f in p):
+            k = by_id[id(f.obs.base)]
+            start = int(np.shares_memory(f.obs, trajs[k].obs) and
+                        (f.obs.__array_interface__["data"][0] - trajs[k].obs.__array_interface__["data"][0])
+                        // trajs[k].obs.strides[0])
+            picks.append((k, start))
+        rec["picks"].append(np.array(picks, np.int64))
+        return pairs
+
+    class _Frag(pc.Fragmenter):
+        def __call__(self, *a):
+            return frag_call(*a)
+
+    orig_train = trainer.train
+
+    def train_call(dataset, epoch_multiplier=1.0):
+        orig_train(dataset, epoch_multiplier)
+        sd = {k: v.detach().numpy().copy() for k, v in model.state_dict().items()}
+        rec["params"].append(sd)
+        st = trainer.optim.state
+        ps = list(trainer.optim.param_groups[0]["params"])
+        rec["adam"].append({"step": int(st[ps[0]]["step"]),
+                            "exp_avg": np.concatenate([st[p]["exp_avg"].reshape(-1).numpy() for p in ps]),
+                            "exp_avg_sq": np.concatenate([st[p]["exp_avg_sq"].reshape(-1).numpy() for p in ps])})
+
+    trainer.train = train_call
+    orig_gather = gatherer.__call__
+
+    class _Gath(pc.PreferenceGatherer):
+        def __call__(self, pairs):
+            p = orig_gather(pairs)
+            rec["gathered"].append(np.asarray(p, np.float32))
+            return p
+
+    orig_dump = logger.dump
+
+    def dump(step=0):
+        rec["dumps"].append({k: float(v) for k, v in logger.default_logger.name_to_value.items()})
+        orig_dump(step)
+
+    logger.dump = dump
+    algo = pc.PreferenceComparisons(gen, model, num_iterations=cfg["iters"], fragmenter=_Frag(custom_logger=logger),
+                                    preference_gatherer=_Gath(custom_logger=logger), reward_trainer=trainer,
+                                    comparison_queue_size=cfg["queue"], fragment_length=cfg["frag"],
+                                    initial_epoch_multiplier=cfg["init_mult"], custom_logger=logger)
+    for c in (algo.fragmenter, algo.preference_gatherer):
+        c.logger = logger
+    trainer.train = train_call
+    logger.dump = dump
+    import io
+    import contextlib
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        result = algo.train(total_timesteps=0, total_comparisons=cfg["comparisons"])
+    schedule = json.loads(buf.getvalue().split("Query schedule: ")[1].split("\n")[0])
+
+    out = {"cfg": json.dumps(cfg), "schedule": np.array(schedule, np.int64),
+           "result": np.array([result["reward_loss"], result["reward_accuracy"]], np.float64),
+           "n_iters": np.int64(len(schedule))}
+    for k, (o, a, w) in enumerate(raw):
+        out[f"traj{k}_obs"], out[f"traj{k}_acts"], out[f"traj{k}_rews"] = o, a, w
+    for i in range(len(schedule)):
+        out[f"it{i}_picks"] = rec["picks"][i]
+        out[f"it{i}_prefs"] = rec["gathered"][i]
+        for k, v in rec["params"][i].items():
+            out[f"it{i}_param/{k}"] = v
+        for k, v in rec["adam"][i].items():
+            out[f"it{i}_adam/{k}"] = np.asarray(v)
+        d = rec["dumps"][i]
+        keys = sorted(d)
+        out[f"it{i}_log_keys"] = np.array(keys)
+        out[f"it{i}_log_vals"] = np.array([d[k] for k in keys], np.float64)
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+    print(name, "schedule", schedule, "result", result, "bytes", os.path.getsize(os.path.join(HERE, name + ".npz")))
+
+
+def main():
+    import tempfile
+    mods = install()
+    tmp = tempfile.mkdtemp()
+    for name, cfg in CASES.items():
+        run_case(name, cfg, *mods, tmp)
+
+
+if __name__ == "__main__":
+    main()
