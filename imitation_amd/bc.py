@@ -77,6 +77,7 @@ class BC:
         require_device(self._device)
         self._logger = custom_logger or imit_logger.configure()
         self._stream: Optional[_EpochIndexStream] = None
+        self._row_map: Optional[np.ndarray] = None
         if demonstrations is not None:
             self.set_demonstrations(demonstrations)
         self.action_space, self.observation_space, self.rng = action_space, observation_space, rng
@@ -124,6 +125,22 @@ class BC:
     def logger(self):
         return self._logger
 
+    @logger.setter
+    def logger(self, value) -> None:
+        self._logger = value
+
+    def __getstate__(self):
+        """State without the logger (open files), as the reference's `BaseImitationAlgorithm.__getstate__`."""
+        d = dict(self.__dict__)
+        del d["_logger"]
+        if d.get("_row_map") is not None:   # tables handed over by `set_demonstrations_device` belong to their owner
+            d["_demo_obs"] = d["_demo_acts"] = d["_row_map"] = d["_stream"] = None
+        return d
+
+    def __setstate__(self, state) -> None:
+        self.__dict__.update(state)
+        self._logger = None    # (assign `logger` before training: unpickling opens no log directory of its own)
+
     def set_demonstrations(self, demonstrations) -> None:
         if isinstance(demonstrations, (list, tuple)) and len(demonstrations) and hasattr(demonstrations[0], "terminal"):
             demonstrations = dt.flatten_trajectories(list(demonstrations))
@@ -132,6 +149,27 @@ class BC:
         self._stream = _EpochIndexStream(n, self.minibatch_size)
         self._demo_host = (obs, acts)
         self._demo_obs = None      # device tables are laid out for the policy: uploaded on first use
+        self._row_map = None
+
+    def set_demonstrations_device(self, obs: th.Tensor, acts: th.Tensor, row_map: np.ndarray) -> None:
+        """Demonstrations that already live on the device: `obs [cap, D]` / `acts [cap, A]` fp32 tables (a Discrete
+        action is its index) and a host `row_map` -- dataset position p is table row `row_map[p]`; rows the map does not
+        name are not part of the dataset. Epochs draw their permutation over `len(row_map)` positions exactly as
+        `set_demonstrations` does and compose it with the map before the gather (`DAggerTrainer` keeps its aggregated
+        dataset in such a table across rounds)."""
+        if self._image:
+            raise NotImplementedError("device-resident demonstration tables hold flat fp32 observations")
+        row_map = np.ascontiguousarray(row_map, dtype=np.int64)
+        assert obs.dim() == 2 and acts.dim() == 2 and obs.dtype == acts.dtype == th.float32
+        assert obs.is_contiguous() and acts.is_contiguous() and obs.device.type == "cuda"
+        assert row_map.ndim == 1 and (len(row_map) == 0 or (row_map.min() >= 0 and row_map.max() < min(len(obs), len(acts))))
+        self._stream = _EpochIndexStream(len(row_map), self.minibatch_size)
+        self._demo_host = None
+        self._demo_obs, self._demo_acts, self._row_map = obs, acts, row_map
+        for name, width in (("_obs_b", obs.shape[1]), ("_acts_b", acts.shape[1])):   # batch buffers: kept while they fit
+            buf = getattr(self, name, None)
+            if buf is None or buf.shape != (self.minibatch_size, width):
+                setattr(self, name, th.empty(self.minibatch_size, width, device=self._device))
 
     def _upload(self) -> None:
         obs, acts = self._demo_host
@@ -149,6 +187,8 @@ class BC:
         B = len(idx)
         if self._demo_obs is None:
             self._upload()
+        if self._row_map is not None:   # (`set_demonstrations_device`: dataset position -> table row)
+            idx = self._row_map[idx]
         i = th.as_tensor(idx).to(self._device, non_blocking=True)
         acts = self._acts_b[:B]
         if self._image:   # uint8 frames: a byte gather (data movement only)

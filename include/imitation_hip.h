@@ -490,6 +490,26 @@ int ia_airl_round(const ia_airl_update_args* a, int n, void* stream);
 int ia_policy_logits(const ia_policy_desc* d, const float* params, const float* params_t, const float* norm_mean,
                      const float* norm_var, const float* obs, int n, float* logits, float* values, void* stream);
 
+/* DAgger collection step (dagger.hip): ONE launch for the two policy forwards of an environment step. `expert` and
+ * `learner` are fused-shape policies over the same spaces with the same hidden width (else IA_ERR_UNSUPPORTED: the
+ * caller asks the two policies separately); each normalises the observations with its own statistics (or none).
+ *   expert_act[n, W]: the expert's mode -- the clipped mean (Box, W = act_dim) / the arg-max index as a float
+ *                     (Discrete, W = 1): the bits `ia_policy_act` writes to `clipped` for zero noise / a negative uniform;
+ *   actual_act[n, W]: expert_act where mask[i] == 0, else the learner's action sampled from noise[i] ([n, act_dim]
+ *                     standard normal / [n] uniform) and clipped: the bits of `ia_policy_act` on the learner;
+ *   learner_logits != NULL (a Discrete learner sampled on the host): the learner's head outputs [n, act_dim] instead;
+ *                     nothing is sampled, `noise` may be NULL and actual_act == expert_act (the host mixes);
+ *   table_obs / table_acts != NULL: rows base_row .. base_row + n - 1 of the aggregation table ([cap, obs_dim],
+ *                     [cap, W]) receive (obs[i], expert_act[i]); base_row + n <= table_cap is checked here.
+ * A row's outputs depend on neither the other rows nor n. `obs`, `mask`, `noise` and the three outputs may live in
+ * pinned (device-mapped) host memory. */
+int ia_dagger_act(const ia_policy_desc* expert, const float* e_params, const float* e_params_t, const float* e_norm_mean,
+                  const float* e_norm_var, const ia_policy_desc* learner, const float* l_params, const float* l_params_t,
+                  const float* l_norm_mean, const float* l_norm_var, const float* obs, int n, const uint8_t* mask,
+                  const float* noise, const float* low, const float* high, float* expert_act, float* actual_act,
+                  float* learner_logits, float* table_obs, float* table_acts, int64_t base_row, int64_t table_cap,
+                  void* stream);
+
 /* [SB3 RolloutBuffer.compute_returns_and_advantage]: arrays are [T,n] fp32. */
 int ia_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values,
            const float* last_dones, int T, int n, float gamma, float gae_lambda, float* advantages,
