@@ -1,7 +1,8 @@
 """Generates `tests/golden/preference_*.npz` by running the REFERENCE's own `preference_comparisons`
 (`imitation.algorithms.preference_comparisons`, imported unmodified under `oracle.ref_shim`) with a `TrajectoryDataset`
 generator over fixed trajectories. Runs only where the reference sources are present.
-Usage: `python tests/golden/make_golden_preferences.py`.
+Usage: `python tests/golden/make_golden_preferences.py [CASE ...]` (no name: every case; with names, only those files
+are written).
 
 The shim has no `stable_baselines3.common.type_aliases` and its SB3 `Logger` has no `warn`, which the module touches:
 this script adds both in its own process. Each file holds the trajectories, the case's settings, the query schedule,
@@ -34,6 +35,12 @@ CASES = {
     "preference_discrete": dict(obs_dim=4, act_dim=3, discrete=True, norm=True, wrap=False, n_traj=10, horizon=30,
                                 frag=6, iters=2, comparisons=20, batch=8, mb=None, epochs=2, init_mult=2.0,
                                 gamma=0.99, noise=0.0, queue=None, seed=3),
+    # the reference's default sizes (32 pairs a batch, 100-step fragments). Schedule [4, 36]: one minibatch of 4 pairs, then
+    # the 40 pairs as minibatches of 32 (64 fragments) and 8. The generator asks for 2 * 36 * 100 = 7200 transitions in the
+    # second iteration and refuses a dataset that holds fewer: 60 trajectories of 120 steps is the least that passes
+    "preference_default_sizes": dict(obs_dim=17, act_dim=6, discrete=False, norm=True, wrap=False, n_traj=60, horizon=120,
+                                     frag=100, iters=1, comparisons=40, batch=32, mb=None, epochs=1, init_mult=1.0,
+                                     gamma=0.99, noise=0.0, queue=None, seed=4),
 }
 
 
@@ -178,10 +185,14 @@ def run_case(name, cfg, pc, types, reward_nets, networks, imit_logger, tmp):
 
 def main():
     import tempfile
+    names = sys.argv[1:] or list(CASES)
+    unknown = [n for n in names if n not in CASES]
+    if unknown:
+        raise SystemExit(f"unknown case(s) {unknown}; known: {list(CASES)}")
     mods = install()
     tmp = tempfile.mkdtemp()
-    for name, cfg in CASES.items():
-        run_case(name, cfg, *mods, tmp)
+    for name in names:
+        run_case(name, CASES[name], *mods, tmp)
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ from imitation_amd import preference_comparisons as pc
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["preference_basic_rn", "preference_plain_disc_noise_accum", "preference_normalized_queue",
-         "preference_discrete"]
+         "preference_discrete", "preference_default_sizes"]
 
 
 def load_case(name):

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["preference_basic_rn", "preference_plain_disc_noise_accum", "preference_normalized_queue",
-         "preference_discrete"]
+         "preference_discrete", "preference_default_sizes"]
 
 
 # ---------------------------------------------------------------------------------------------- kernel (a)
@@ -241,7 +241,8 @@ def test_preference_comparisons_matches_reference(name):
     _check(*_run(name))
 
 
-@pytest.mark.parametrize("name", ["preference_basic_rn", "preference_plain_disc_noise_accum"])
+@pytest.mark.parametrize("name", ["preference_basic_rn", "preference_plain_disc_noise_accum",
+                                  "preference_default_sizes"])
 def test_module_net_path_matches_reference(name):
     _check(*_run(name, module_net=True))
 
