@@ -252,6 +252,11 @@ _SIGS = {
     "ia_pref_norm_apply_seq": ([_P, _I, _I, _I, _I, _P, _F, _P, _I, _P], C.c_int),
     "ia_adamw_step": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P], C.c_int),
     "ia_reduce_partials_adamw": ([_P, _I, _L, _F, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P], C.c_int),
+    "ia_mce_backup": ([_P, _P, _I, _I, _I, _D, _P, _P, _P, _P], C.c_int),
+    "ia_mce_forward_ws_doubles": ([_I, _I], C.c_int64),
+    "ia_mce_forward": ([_P, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P], C.c_int),
+    "ia_mce_weights": ([_P, _P, _I, _P, _P, _P], C.c_int),
+    "ia_mce_norms": ([_P, _P, _L, _P, _P], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

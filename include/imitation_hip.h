@@ -846,6 +846,27 @@ int ia_reduce_partials_adamw(const float* partials, int splits, int64_t n, float
                              float* exp_avg, float* exp_avg_sq, float beta1, float beta2, float eps, float decay,
                              float step_size, float bc2_sqrt, void* stream);
 
+/* Finite-horizon tabular maximum-causal-entropy planning (algorithms/mce_irl.py). Every table is float64, row-major:
+ * T [S, A, S] (transition probabilities, T[s, a, s']), V [H, S], Q and pi [H, S, A], D [H + 1, S]. No kernel behind these
+ * entries waits on another workgroup; timesteps are ordered by launch order on `stream`, and the results repeat bit for
+ * bit (sums across workgroups go through slabs added in a fixed order, never through floating-point atomics).
+ * ia_mce_backup: mce_partition_fh (:38-93) -- Q[H-1, s, a] = r[s]; Q[t, s, a] = r[s] + discount * sum_s' T[s, a, s'] V[t+1, s'];
+ * V[t, s] = logsumexp_a Q[t, s, :] (max-subtracted like SciPy); pi = exp(Q - V). `reward` [S] is float32 and widened on load.
+ * One launch per timestep; A <= 1024 (IA_ERR_UNSUPPORTED above). */
+int ia_mce_backup(const double* T, const float* reward, int S, int A, int H, double discount, double* V, double* Q,
+                  double* pi, void* stream);
+/* ia_mce_forward: mce_occupancy_measures (:96-144) -- D[0] = init; D[t+1, s'] = sum_{s, a} D[t, s] pi[t, s, a] T[s, a, s'];
+ * Dcum[s] = sum_t discount^t D[t, s] over the H + 1 rows (rollout.discounted_sum: a plain sum when discount == 1, else
+ * Horner's form). ws: ia_mce_forward_ws_doubles doubles of scratch (slab sums; no need to clear it). */
+int64_t ia_mce_forward_ws_doubles(int S, int A);
+int ia_mce_forward(const double* T, const double* pi, const double* init, int S, int A, int H, double discount,
+                   double* D, double* Dcum, double* ws, void* stream);
+/* The reward net's dOut and the termination statistics of MCEIRL.train (:467-544), `stats` a row of three doubles:
+ * ia_mce_weights: w[s] = (float)(Dcum[s] - demo_om[s]); stats[0] = max_s |demo_om[s] - Dcum[s]| (NaN if any is).
+ * ia_mce_norms: stats[1], stats[2] = the float32 L2 norms (util.tensor_iter_norm) of `grads` and `params`, n floats each. */
+int ia_mce_weights(const double* Dcum, const double* demo_om, int S, float* w, double* stats, void* stream);
+int ia_mce_norms(const float* grads, const float* params, int64_t n, double* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
