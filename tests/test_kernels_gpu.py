@@ -116,6 +116,109 @@ def test_gemm_tn_splitk_and_bias_sums(M, N, K, splits):
     th.testing.assert_close(db.sum(0).cpu(), A.double().sum(0).float(), rtol=3e-5, atol=3e-5 * math.sqrt(K))
 
 
+def _bits_equal(a, b):
+    return th.equal(a.view(th.int32), b.view(th.int32))
+
+
+def _padded(x, ld, offset=0):
+    """`x` [rows, n] on the device as rows of stride `ld` (padding NaN: an operand element the product does not define
+    must not reach it), starting `offset` floats into its allocation. Returns the flat view whose pointer is passed."""
+    rows, n = x.shape
+    buf = th.full((offset + rows * ld,), float("nan"), device=DEV)
+    buf[offset:].view(rows, ld)[:, :n] = x.to(DEV)
+    _KEEP.append(buf)
+    return buf[offset:]
+
+
+def _gemm_strided(mode, A, B, M, N, K, lda, ldb, ldc, bias=None, act=0, P=None, ldp=0, splits=1, want_db=False,
+                  a_off=0, b_off=0):
+    """`ia_gemm_f32` on operands with the given leading dimensions / base offsets, launched twice into NaN-filled
+    outputs: returns (C [slabs, M, ldc], dbias [slabs, M] or None) after checking that the two launches agree bit for
+    bit and that the `ldc` padding still holds the fill."""
+    dA, dB = _padded(A, lda, a_off), _padded(B, ldb, b_off)
+    dP = _padded(P, ldp) if P is not None else None
+    dbias = dev(bias) if bias is not None else None
+    _KEEP.append(dbias)
+    slabs = splits if mode == 2 else 1
+    outs = []
+    for _ in range(2):
+        Cs = th.full((slabs, M, ldc), float("nan"), device=DEV)
+        db = th.full((slabs, M), float("nan"), device=DEV) if want_db else None
+        L.call("ia_gemm_f32", mode, L.ptr(dA), lda, L.ptr(dB), ldb, L.ptr(Cs), ldc, M, N, K, L.ptr(dbias), act, L.ptr(dP), ldp,
+               splits, L.ptr(db), L.stream())
+        th.cuda.synchronize()
+        outs.append((Cs, db))
+    (Cs, db), (Cs2, db2) = outs
+    assert _bits_equal(Cs, Cs2) and (db is None or _bits_equal(db, db2)), "two launches differ"
+    assert bool(th.isfinite(Cs[..., :N]).all()), "defined elements not finite"
+    assert bool(th.isnan(Cs[..., N:]).all()), "ldc padding overwritten"
+    assert db is None or bool(th.isfinite(db).all())
+    return Cs[..., :N].cpu(), (db.cpu() if db is not None else None)
+
+
+def _check_three_modes(M, N, K, pad_a, pad_b, pad_c, pad_p, a_off=0, b_off=0, splits=3):
+    """NT (bias + ReLU), NN (tanh') and TN (split, dbias) of one (M, N, K) against float64; leading dimension =
+    extent + pad (rounded up to a multiple of 4 for pad = None)."""
+    ld = lambda n, pad: (n + 3) // 4 * 4 if pad is None else n + pad
+    tol = dict(rtol=2e-5, atol=2e-5 * math.sqrt(K))
+    A, B, b = rnd(M, K, seed=1), rnd(N, K, seed=2), rnd(N, seed=3)
+    got, _ = _gemm_strided(0, A, B, M, N, K, ld(K, pad_a), ld(K, pad_b), ld(N, pad_c), bias=b, act=1, a_off=a_off, b_off=b_off)
+    th.testing.assert_close(got[0], th.relu(A.double() @ B.double().T + b.double()).float(), **tol)
+    Bn, P = rnd(K, N, seed=2), th.tanh(rnd(M, N, seed=3))
+    got, _ = _gemm_strided(1, A, Bn, M, N, K, ld(K, pad_a), ld(N, pad_b), ld(N, pad_c), act=2, P=P, ldp=ld(N, pad_p),
+                           a_off=a_off, b_off=b_off)
+    th.testing.assert_close(got[0], ((A.double() @ Bn.double()) * (1 - P.double() ** 2)).float(), **tol)
+    At, Bt = rnd(K, M, seed=1), rnd(K, N, seed=2)
+    got, db = _gemm_strided(2, At, Bt, M, N, K, ld(M, pad_a), ld(N, pad_b), ld(N, pad_c), splits=splits, want_db=True,
+                            a_off=a_off, b_off=b_off)      # slab s at C + s * M * ldc
+    th.testing.assert_close(got.double().sum(0).float(), (At.double().T @ Bt.double()).float(), rtol=3e-5, atol=3e-5 * math.sqrt(K))
+    th.testing.assert_close(db.double().sum(0).float(), At.double().sum(0).float(), rtol=3e-5, atol=3e-5 * math.sqrt(K))
+
+
+DENSE_LD_SHAPES = [(130, 70, 64), (64, 64, 32), (33, 17, 45)]
+
+
+@pytest.mark.parametrize("M,N,K", DENSE_LD_SHAPES)
+def test_gemm_leading_dimensions_larger_than_the_extent(M, N, K):
+    """Activations in padded tiles (gather-concat, gradient penalty): lda = ext + 4, ldb = ext + 8, ldc = N + 3,
+    ldp = N + 5; operand padding is NaN, output padding must keep its NaN."""
+    _check_three_modes(M, N, K, 4, 8, 3, 5)
+
+
+@pytest.mark.parametrize("M,N,K", DENSE_LD_SHAPES)
+def test_gemm_rows_that_are_no_16_byte_multiple(M, N, K):
+    """lda = extent + 1: no row of A but the first is 16-byte aligned, every load takes the scalar-guard path."""
+    _check_three_modes(M, N, K, 1, 8, 3, 5)
+
+
+@pytest.mark.parametrize("a_off,b_off", [(1, 0), (0, 1), (1, 1)])
+@pytest.mark.parametrize("M,N,K", DENSE_LD_SHAPES[:2])
+def test_gemm_operands_at_a_4_byte_offset(M, N, K, a_off, b_off):
+    """Weights are sub-views of a flat parameter vector: base pointer 4 bytes past a 16-byte boundary, ld % 4 == 0."""
+    _check_three_modes(M, N, K, None, None, 0, 0, a_off=a_off, b_off=b_off)
+
+
+@pytest.mark.parametrize("M,N,K", DENSE_LD_SHAPES)
+def test_gemm_nt_without_bias(M, N, K):
+    A, B = rnd(M, K, seed=1), rnd(N, K, seed=2)
+    for act, f in [(0, lambda x: x), (1, th.relu), (2, th.tanh), (3, F.softplus)]:
+        got, _ = _gemm_strided(0, A, B, M, N, K, K, K, N, bias=None, act=act)
+        th.testing.assert_close(got[0], f(A.double() @ B.double().T).float(), rtol=2e-5, atol=2e-5 * math.sqrt(K))
+
+
+@pytest.mark.parametrize("M,N,K", [(257, 131, 77), (256, 256, 64)])
+@pytest.mark.parametrize("cfg", range(6))
+def test_gemm_forced_tile_configs(cfg, M, N, K):
+    """Every tile config `ia_gemm_set_config` can force (0: 128x128, 1: 64x64, 2: 128x32, 3: 32x128, 4: 64x128,
+    5: 128x64; the tuning tools decide by them) computes the product in all three modes. The setting is process-global:
+    restored whatever happens."""
+    try:
+        L.call("ia_gemm_set_config", cfg)
+        _check_three_modes(M, N, K, 0, 0, 0, 0, splits=3)
+    finally:
+        L.call("ia_gemm_set_config", -1)
+
+
 def _torch_mlp(dims, act):
     layers = []
     for i in range(len(dims) - 1):
