@@ -1807,13 +1807,21 @@ __device__ __forceinline__ void chain_stage_rows(const ia_policy_desc& d, const 
 // grid wait, no re-read through L2. The loss-statistic partials (for the statistics workgroup) are stored write-through;
 // the caller drains them (`vmcnt(0)` in every wave) at the END of the step, where it waits for the prefetched rows
 // anyway, and arrives after that -- no release fence (cdna_hip_programming.md G16 R1), no acknowledgement on the chain.
-template <int KS1, bool LOCAL, bool SMALL = false, bool STAGED = false>
+// TSPLIT (several gradient workgroups, one process; `ppo_update_split_kernel`): the workgroup serves ONE tower (`split_tw`)
+// of its row block, its twin on another compute unit the other. Waves 0-3 run the tower's chain (q = wave: one chain wave
+// per SIMD, the matrix pipe to itself); waves 4-7 are helpers: they skip the layer chain, meet the same block barriers and
+// take their share of the tower's gradient tiles, column sums and dots. Every tile keeps its MFMA order and every sum its
+// order of additions, so the slab words -- the twins write disjoint elements of the row block's slab under the same
+// sequence number -- carry the bits of the two-tower form.
+template <int KS1, bool LOCAL, bool SMALL = false, bool STAGED = false, bool TSPLIT = false>
 __device__ __forceinline__ void mfma32_minibatch_chain(
     const ia_policy_desc& d, const float* __restrict__ nm, const float* __restrict__ nv, const float adv_mean,
     const float adv_std, const MbRows rows, const int i0_in, const int row_lim, const int normalize_adv, const float clip,
     const float ent_coef, const float vf_coef, float* __restrict__ slab_g, float* __restrict__ statpart,
     float* __restrict__ lds_in, const float* __restrict__ sP_in, float* __restrict__ stg_in,
-    const int opaque_zero, long long* __restrict__ tstamp, const unsigned ll_seq, const bool ll_xcd = false) {
+    const int opaque_zero, long long* __restrict__ tstamp, const unsigned ll_seq, const bool ll_xcd = false,
+    const int split_tw = 0) {
+  static_assert(!TSPLIT || (!LOCAL && !SMALL && STAGED), "one tower per workgroup: several gradient workgroups only");
   // `ll_xcd` (wave-uniform): every gradient workgroup of the launch sits on this XCD (the kernel has checked): the slab
   // words are stored at workgroup scope -- they stay in the XCD's L2 instead of costing a fabric write each.
   // `i0_in`: first minibatch row of this workgroup; `row_lim`: rows at or beyond it are not this workgroup's (the
@@ -1844,7 +1852,8 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
   // uniform branch around the chain alone cost ~1 us per step at config P -- measured --, and full workgroups want the
   // OTHER numbering: SIMD k then hosts (policy, k) and (value, k), complementary work, instead of two waves of one tower
   // in lockstep)
-  const int tw = SMALL ? (wv & 1) : (wv >> 2), q = SMALL ? (wv >> 1) : (wv & 3);
+  const int tw = TSPLIT ? split_tw : (SMALL ? (wv & 1) : (wv >> 2)), q = SMALL ? (wv >> 1) : (wv & 3);
+  const bool helper = TSPLIT && wv >= 4;   // wave-uniform; compiled out of the two-tower instantiations
   const int li = lane & 15, lk = lane >> 4;
   const int D = d.obs_dim, A = d.act_dim;
   const PolOff o = pol_offsets(D, A, H, d.discrete);
@@ -1874,7 +1883,8 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
   // latencies off the policy wave's path: 7.53 -> 7.40 us per step on the tuned AIRL file. With full workgroups the two towers
   // of a row quarter SHARE a SIMD and the hand-over measures 2-4 % slower (`profiles/r06_ppo_ab.md`): they keep the old split.
   constexpr bool HANDOVER = SMALL;
-  if (tw == 0) {   // staged by the prefetch (LDS-direct loads); unconditional, clamped
+  if (helper) {   // (TSPLIT: no rows, no fragments, no constants -- straight to the barrier the staged rows are published by)
+  } else if (tw == 0) {   // staged by the prefetch (LDS-direct loads); unconditional, clamped
     r_oldlp = stg[UpdStage::oldlp + lrow];
     if constexpr (!HANDOVER) r_adv = stg[UpdStage::adv + lrow];
 #pragma unroll
@@ -1887,7 +1897,7 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
 
   IA_TS(9);
   // (SMALL: rows 16.. do not exist in any minibatch of the launch; the caller zeroed every tile once, their waves idle)
-  const bool idle = SMALL && q > 0;   // wave-uniform; compiled out of the general instantiations
+  const bool idle = (SMALL && q > 0) || helper;   // wave-uniform; compiled out of the general instantiations
   // ---- stage this wave's 16 feature rows (normalised) into the x tile; clear its rows of the small tiles (STAGED: the
   // caller did that already -- several gradient workgroups stage the NEXT minibatch while the sum vector is in flight)
   if constexpr (!STAGED) chain_stage_rows<SMALL>(d, nm, nv, i0, row_lim, lds, stg, tw, q, lane);
@@ -1904,6 +1914,9 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
   constexpr int KT1 = KS1 / 4;   // K tiles (16 input columns each) the first layer's fragments are sized for
   float fW1[KT1][2][4], fW2[2][2][4], fW2T[2][2][4], fHead[2][4], fHeadT[2][4], b1c[2][4], b2c[2][4], hb[4];
   // (biases: initial values of the layers' accumulators -- C layout, output 16 t + 4 lk + r -- dead once the layer starts)
+  const int head_base = tw == 0 ? o.aW + min(li, A - 1) * H : o.cW;
+  float c_ivar[4] = {1.f, 1.f, 1.f, 1.f}, c_logsd[4] = {0.f, 0.f, 0.f, 0.f};   // of this lane's actions 4 lk + j (policy waves; read behind the barrier)
+  if (!helper) {
 #pragma unroll
   for (int kt = 0; kt < KT1; ++kt) {
     if (4 * kt < S1) {
@@ -1918,7 +1931,6 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
         for (int r = 0; r < 4; ++r) fW1[kt][t][r] = 0.f;
     }
   }
-  const int head_base = tw == 0 ? o.aW + min(li, A - 1) * H : o.cW;
   // (the fragments of layer 2 and of the head are requested behind the previous layer's MFMAs -- their LDS latency
   //  passes under that layer's tanh -- instead of here: 40 registers less across the first layer)
 #pragma unroll
@@ -1933,7 +1945,6 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) fW1[kt][t][r] = (16 * kt + 4 * lk + r < D) ? fW1[kt][t][r] : 0.f;
-  float c_ivar[4] = {1.f, 1.f, 1.f, 1.f}, c_logsd[4] = {0.f, 0.f, 0.f, 0.f};   // of this lane's actions 4 lk + j (policy waves; read behind the barrier)
   if constexpr (HANDOVER) {
     if (tw != 0) {
       if (!idle) {   // this wave's 16 rows: the advantage as the loss uses it
@@ -1967,6 +1978,7 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
       c_logsd[j] = __shfl(my_logsd, 4 * lk + j, 64);
     }
   }
+  }   // (!helper)
   IA_TS(11);
   // the x rows of this wave were written by the two waves (tower 0 / tower 1) that share q
   __syncthreads();
@@ -2401,6 +2413,78 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
     sm += __shfl_xor(sm, 32, 64);
     return sm;   // (lanes j and j + 32: feature j's sum over the 64 rows)
   };
+  if constexpr (TSPLIT) {
+    // One tower per workgroup: the tower's tiles -- 4 of dW2, the policy head's 2, the first layer's (without the narrow
+    // second K tile's, which are dots) -- are dealt over the EIGHT waves, wave w taking tiles w, w + 8, ...: one tile per
+    // wave at <= 32 observation columns (policy 8, value 6), two MFMA tiles per SIMD and step instead of four. Column sums
+    // and dots sit on the helper waves first (value tower: on the two waves without a tile).
+    const int KT = (D + 15) >> 4;
+    const int nh = tw == 0 ? 2 : 0;
+    const int NT = 4 + nh + (narrow ? 2 : 2 * KT);
+    for (int t = wv; t < NT; t += 8) {   // (wave-uniform)
+      const float* U;
+      const float* V;
+      int uf, vf, base, stride, rowlim = 16;
+      bool colok = true;
+      if (t < 4) {   // dW2[jt2][kt2] = dz2^T a1
+        U = dz2t; uf = (t >> 1) * 16; V = a1t; vf = (t & 1) * 16;
+        base = oW2 + (t >> 1) * 16 * H + (t & 1) * 16; stride = H;
+      } else if (t < 4 + nh) {   // dWa[a][h] = sum_r dout[r][a] a2[r][h], 16 h-columns per tile
+        const int ht = t - 4;
+        U = lds + L::dout; uf = 0; V = a2t; vf = ht * 16;
+        base = o.aW + ht * 16; stride = H; rowlim = A;
+      } else {   // dW1[jt][kt] = dz1^T x  (narrow: tiles (jt, kt = 1) are the VALU dots below)
+        const int n = t - 4 - nh, ti = narrow ? n * KT : n;
+        const int jt = ti / KT, kt = ti - jt * KT;
+        U = dz1t; uf = jt * 16; V = lds + L::x; vf = kt * 16;
+        base = oW1 + jt * 16 * D + kt * 16; stride = D; colok = kt * 16 + li < D;
+      }
+      const f32x4 g = outer16(U, uf + li, V, vf + li);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (lk * 4 + r < rowlim && colok) put(slab + (base + (lk * 4 + r) * stride + li), g[r]);
+    }
+    IA_TS(7);
+    if (narrow)   // dW1[j][16 + c'], c' < D - 16 <= 4: all 32 rows j of the tower at once, a column per chain wave
+      for (int c = 16; c < D; ++c)
+        if (wv == ((c - 16) & 3)) {
+          const float sm = dot32(dz1t, lds + L::x + c * L::RS);
+          if (lane < 32) put(slab + (oW1 + lane * D + c), sm);
+        }
+    if (tw == 0) {
+      if (wv == 4) colsum64(lds + L::dout, A, slab + o.ab);
+      if (wv == 5 && !d.discrete) colsum64(lds + L::aux, A, slab + o.log_std);
+    } else if (wv == 6) {   // dcW[h] = sum_r dv[r] a2[r][h]: 32 numbers
+      const float sm = dot32(a2t, lds + L::misc + L::RS);
+      if (lane < 32) put(slab + (o.cW + lane), sm);
+    }
+    if (wv == 6) colsum64_wide(dz2t, slab + ob2);
+    if (wv == 7) colsum64_wide(dz1t, slab + ob1);
+    if (wv == (tw == 0 ? 3 : 7)) {
+      // The misc tile by owner: columns 2..5 (loss statistics -> tail slots 0, 2, 3, 4) are this row block's policy
+      // workgroup's, column 1 (-> cb) and column 6 (value loss -> tail slot 1) its value workgroup's; the other tower's
+      // columns are the zeros the staging left here. Lane c < 6 handles column 1 + c: per-column order as in the
+      // two-tower form.
+      const int c = lane & 15, part = lane >> 4;
+      const float* cp = lds + L::misc + (1 + min(c, 5)) * L::RS + part * 16;
+      f32x4 t[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) t[i] = rd4(cp + 4 * i);
+      __builtin_amdgcn_sched_barrier(0);
+      float sm = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) sm += (t[i][0] + t[i][1]) + (t[i][2] + t[i][3]);
+      sm = c < 6 ? sm : 0.f;
+      sm += __shfl_xor(sm, 16, 64);
+      sm += __shfl_xor(sm, 32, 64);
+      if (tw != 0 && lane == 0) put(slab + (o.cb), sm);
+      if (tw == 0 ? (lane >= 1 && lane < 5) : lane == 5) {
+        const int m = lane - 1;                      // misc column 2 + m
+        const int slot = m == 0 ? 0 : (m == 4 ? 1 : m + 1);
+        ll_store_agent(slab64 + (((o.total + 3) & ~3) + slot), sm, ll_seq);   // the slab's tail
+      }
+    }
+  } else {
   if (tw == 0) {
     const bool head_tile = TILES2 ? (q & 1) != 0 : q < 2;   // dWa[a][h] = sum_r dout[r][a] a2[r][h], 16 h-columns per wave
     if (head_tile) {
@@ -2482,6 +2566,7 @@ __device__ __forceinline__ void mfma32_minibatch_chain(
     }
     if (q == 2) colsum64_wide(dz1t, slab + ob1);
   }
+  }   // (!TSPLIT)
   __syncthreads();
   IA_TS(8);
 #undef IA_TS
@@ -4572,9 +4657,19 @@ __global__ __launch_bounds__(64 * NW) void ppo_epoch_ll2_kernel(
 
 // TIMING = false (production): the phase-clock accumulators (24 VGPRs of `tacc` alone) and every stamp are
 // compiled out -- the measurement build is a separate instantiation picked only while ia_ppo_debug_timing is on.
-template <int NPT, bool TIMING, int KS1, bool LOCAL, bool SHARD = false, bool SMALL = false>
-__global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
-    ia_policy_desc d, float* __restrict__ P, float* __restrict__ Pt, float* __restrict__ m, float* __restrict__ v,
+// TSPLIT (`ppo_update_split_kernel`; several gradient workgroups, one process): TWO gradient workgroups per 64-row block,
+// one per tower -- workgroup g serves row block g >> 1, tower g & 1 -- so that every SIMD's matrix pipe carries one chain
+// wave and half the tower's gradient tiles (`mfma32_minibatch_chain`). The grid is 2 nblk gradient workgroups + the
+// statistics workgroup + two workgroups per statistics slice (see the slicers). The slabs stay one per ROW BLOCK: the twins write disjoint elements of their block's
+// slab (own tower's parameters, own loss statistics), every word by exactly one of them under the step's sequence number.
+// Hop 1's slices run over all 2 nblk workgroups (each sums its slice of the nblk slabs in slab order 0 .. nblk - 1); hop 2,
+// the norm, the clip and Adam on ALL parameters are the two-tower form's in every workgroup, and so is every bit of the
+// result. The parity argument holds with 2 nblk owners: a word of step s + 2 is written only after every owner has
+// published its slice of step s + 1 (hop 2 polls the WHOLE sum vector), hence has read all slabs of step s + 1 -- and a
+// workgroup writes its slab of step s + 1 only behind its own hop 2 of step s, so nobody still reads the buffer.
+template <int NPT, bool TIMING, int KS1, bool LOCAL, bool SHARD, bool SMALL, bool TSPLIT>
+__device__ __forceinline__ void ppo_update_body(
+    const ia_policy_desc& d, float* __restrict__ P, float* __restrict__ Pt, float* __restrict__ m, float* __restrict__ v,
     float* __restrict__ nm, float* __restrict__ nv, int32_t* __restrict__ ncount, int update_norm,
     const float* __restrict__ obs, const float* __restrict__ actions, const float* __restrict__ old_logp,
     const float* __restrict__ adv, const float* __restrict__ ret, const int64_t* __restrict__ perm, int T, int n_envs,
@@ -4598,6 +4693,10 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
   // on one XCD (hardware deals consecutive block ids round-robin over the 8 XCDs) and share its L2.
   if (xcd_pack && (blockIdx.x & 7)) return;
   const int vb = xcd_pack ? blockIdx.x >> 3 : blockIdx.x;
+  static_assert(!TSPLIT || (!LOCAL && !SHARD && !SMALL), "one tower per workgroup: several gradient workgroups, one process");
+  const int ngw = TSPLIT ? 2 * nblk : nblk;   // gradient workgroups
+  const int rb = TSPLIT ? vb >> 1 : vb;       // this gradient workgroup's row block
+  const int split_tw = TSPLIT ? (vb & 1) : 0;   // ... and (TSPLIT) its tower
   const int tid = threadIdx.x;
   const int D = d.obs_dim;
   const PolOff o = pol_offsets(D, d.act_dim, H, d.discrete);
@@ -4616,7 +4715,7 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
   // they stay in the XCD's L2, the coherence point of its compute units, and the polls (agent scope: past L1) find them
   // there. One exchange per launch; any other placement keeps the agent-scope stores.
   bool ll_xcd = false;
-  if constexpr (!LOCAL) {
+  if constexpr (!LOCAL && !TSPLIT) {
     if (xcd_pack && vb < nblk && nblk <= 64) {
       __shared__ int s_xcd;
       unsigned xcc;
@@ -4710,7 +4809,7 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
     }
   };
 
-  if (vb == nblk) {  // ---------------- statistics block
+  if (vb == ngw) {  // ---------------- statistics block
     // It also writes the loss statistics of finished steps (all but the last one of the launch):
     // step q's partials and its (norm, coef) pair are published by barrier q+1's release fences.
     int q = 0;
@@ -4838,10 +4937,18 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
     drain(n_steps - 1);  // the last step's statistics are written by gradient block 0 itself
     return;
   }
-  if (vb > nblk) {  // ---------------- statistics slicers (large minibatches only)
-    const int j = vb - nblk - 1;
+  if (vb > ngw) {  // ---------------- statistics slicers (large minibatches only)
+    // TSPLIT: TWO workgroups per slice, one for the even steps and one for the odd ones. A slicer needs ~11 us for the
+    // gathered moments of its 512 rows -- under the two-tower form's 13.6 us step, but the bound of the whole update once
+    // the step is shorter (measured: the statistics workgroup then never waits for a free ring slot and the gradient
+    // workgroups wait for IT). The partial slots are per step, so the two write different ones; a slice's progress word is
+    // published in step order (the odd steps' workgroup waits for the even steps' word and vice versa: the bounded spin of
+    // every other wait here). Same moments into the same slots: the merged statistics keep their bits.
+    constexpr int NPH = TSPLIT ? 2 : 1;
+    const int jj = vb - ngw - 1;
+    const int j = jj / NPH;
     if (j >= n_slices) return;
-    for (int s = 0; s < n_steps; ++s) {
+    for (int s = jj - j * NPH; s < n_steps; s += NPH) {
       const MbRows r = rows_of(s);
       const int r0 = j * UPD_SLICE;
       const int nr = min(UPD_SLICE, r.batch - r0);
@@ -4858,7 +4965,9 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
       __syncthreads();
       if (tid == 0) {
         __threadfence();
-        __hip_atomic_store(sliced + j, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // (a failed wait leaves the word behind for good: the error word is set, every other workgroup leaves on it)
+        if (NPH == 1 || s == 0 || spin_until(sliced + j, (unsigned)s, err))
+          __hip_atomic_store(sliced + j, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
     return;
@@ -4905,7 +5014,7 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
       int tz;   // opaque zero: the reciprocal of T behind `f / T` is re-derived per step instead of being spilled
       asm volatile("s_mov_b32 %0, 0" : "=s"(tz));
       const unsigned Tq = (unsigned)(T + tz);
-      const int i0 = row_lo + vb * ROWS;
+      const int i0 = row_lo + rb * ROWS;
       int src = 0;
       if (i0 + lane < row_lim(r)) {
         const long long flat = r.idx[i0 + lane];
@@ -5045,7 +5154,7 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
         int zz;
         asm volatile("s_mov_b32 %0, 0" : "=s"(zz));
         const int wv_ = __builtin_amdgcn_readfirstlane((tid + zz) >> 6);
-        chain_stage_rows<false>(d, stg + UpdStage::ring, stg + UpdStage::ring + MAXD, row_lo + vb * ROWS, row_lim(r), lds, stg,
+        chain_stage_rows<false>(d, stg + UpdStage::ring, stg + UpdStage::ring + MAXD, row_lo + rb * ROWS, row_lim(r), lds, stg,
                                 wv_ >> 2, wv_ & 3, lane);
       }
     }
@@ -5074,10 +5183,11 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
     float* stat_base = w.statpart + (s % UPD_SD) * nblk * 8;
     int oz;
     asm volatile("s_mov_b32 %0, 0" : "=s"(oz));
-    mfma32_minibatch_chain<KS1, LOCAL, SMALL, !LOCAL>(d, slot, slot + MAXD, adv_mean, adv_std, r, row_lo + vb * ROWS, row_lim(r),
+    // (TSPLIT: row block 0 has two workgroups; the chain's stamps are workgroup 0's, the policy tower's)
+    mfma32_minibatch_chain<KS1, LOCAL, SMALL, !LOCAL, TSPLIT>(d, slot, slot + MAXD, adv_mean, adv_std, r, row_lo + rb * ROWS, row_lim(r),
                                        normalize_adv, clip, ent_coef, vf_coef,
-                                       reinterpret_cast<float*>(slabs_s + (long long)vb * P8), stat_base + vb * 8, lds, sP,
-                                       stg, oz, tstamp ? tstamp + 16 : nullptr, lseq, ll_xcd);
+                                       reinterpret_cast<float*>(slabs_s + (long long)rb * P8), stat_base + vb * 8, lds, sP,
+                                       stg, oz, (tstamp && (!TSPLIT || vb == 0)) ? tstamp + 16 : nullptr, lseq, ll_xcd, split_tw);
     // (the minibatch ends with a block barrier: the LDS tiles are free; several workgroups: the slab words are on their
     //  way, nobody waits for them here)
     UPD_TS(1);
@@ -5135,7 +5245,7 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
       // for) step s + 1. Row-sharded data parallelism adds one hop between the two: the slice of this RANK's sum goes to every
       // rank's receive area, the slice's owner sums the ranks' words in rank order and publishes the global slice.
       using u64 = unsigned long long;
-      const int SL = (P8 + nblk - 1) / nblk;   // slice length
+      const int SL = (P8 + ngw - 1) / ngw;   // slice length (one slice per gradient workgroup; TSPLIT: two per slab)
       const unsigned rcpSL = 0xffffffffu / (unsigned)SL + 1u;   // = ceil(2^32 / SL), 32-bit divide
       float* red = lds + L::a1;                // scratch [nblk][SL] (the activation tiles are free until the next minibatch)
       auto valid_el = [&](int gi) { return gi < o.total || (gi >= w.P4 && gi < w.P4 + 5); };   // written elements only
@@ -5271,7 +5381,7 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
         int zz;
         asm volatile("s_mov_b32 %0, 0" : "=s"(zz));
         const int wv_ = __builtin_amdgcn_readfirstlane((tid + zz) >> 6);
-        chain_stage_rows<false>(d, stg + UpdStage::ring, stg + UpdStage::ring + MAXD, row_lo + vb * ROWS, row_lim(rn), lds, stg,
+        chain_stage_rows<false>(d, stg + UpdStage::ring, stg + UpdStage::ring + MAXD, row_lo + rb * ROWS, row_lim(rn), lds, stg,
                                 wv_ >> 2, wv_ & 3, lane);
       }
       if (tid == 0) s_pub = stage_ahead ? s + 2 : 0;   // (what `have_ring` is formed from below)
@@ -5555,6 +5665,31 @@ __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(
     }
   }
 }
+
+#define IA_UPD_KERNEL_PARAMS                                                                                              \
+  ia_policy_desc d, float *__restrict__ P, float *__restrict__ Pt, float *__restrict__ m, float *__restrict__ v,         \
+      float *__restrict__ nm, float *__restrict__ nv, int32_t *__restrict__ ncount, int update_norm,                     \
+      const float *__restrict__ obs, const float *__restrict__ actions, const float *__restrict__ old_logp,              \
+      const float *__restrict__ adv, const float *__restrict__ ret, const int64_t *__restrict__ perm, int T, int n_envs, \
+      int normalize_adv, float clip, float ent_coef, float vf_coef, float max_norm, float beta1, float beta2, float eps, \
+      float *__restrict__ ws, int nblk, int n_slices, float *__restrict__ stats, UpdSched sch, int xcd_pack,             \
+      long long *__restrict__ tstamp, ShardArgs sh
+#define IA_UPD_KERNEL_ARGS                                                                                               \
+  d, P, Pt, m, v, nm, nv, ncount, update_norm, obs, actions, old_logp, adv, ret, perm, T, n_envs, normalize_adv, clip,    \
+      ent_coef, vf_coef, max_norm, beta1, beta2, eps, ws, nblk, n_slices, stats, sch, xcd_pack, tstamp, sh
+
+template <int NPT, bool TIMING, int KS1, bool LOCAL, bool SHARD = false, bool SMALL = false>
+__global__ __launch_bounds__(512) void ppo_update_persistent_kernel(IA_UPD_KERNEL_PARAMS) {
+  ppo_update_body<NPT, TIMING, KS1, LOCAL, SHARD, SMALL, false>(IA_UPD_KERNEL_ARGS);
+}
+
+// One tower per gradient workgroup, two workgroups per row block (see `ppo_update_body`, TSPLIT).
+template <int NPT, bool TIMING, int KS1>
+__global__ __launch_bounds__(512) void ppo_update_split_kernel(IA_UPD_KERNEL_PARAMS) {
+  ppo_update_body<NPT, TIMING, KS1, false, false, false, true>(IA_UPD_KERNEL_ARGS);
+}
+#undef IA_UPD_KERNEL_PARAMS
+#undef IA_UPD_KERNEL_ARGS
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
@@ -6282,6 +6417,8 @@ int g_host_tab_next = 0;
 int ia_ppo_update_xcd_pack(int on) { g_upd_xcd_pack = on != 0; return IA_OK; }
 int g_upd_assume_cus = 0;
 int ia_ppo_update_assume_cus(int n) { g_upd_assume_cus = n; return IA_OK; }
+bool g_upd_tower_split = false;   // (ia_ppo_update_tower_split) two gradient workgroups per row block, one per tower, where they fit
+int ia_ppo_update_tower_split(int on) { g_upd_tower_split = on != 0; return IA_OK; }
 
 // A whole PPO.train: n_epochs passes over consecutive minibatches of perm[e][T*n_envs] (SB3
 // RolloutBuffer.get order), in ONE persistent launch per <= UPD_MAX_STEPS optimiser steps.
@@ -6337,6 +6474,16 @@ static int ppo_update_launch(const ia_policy_desc* d, float* params, float* para
   const bool small = local && batch_size <= 16 && !timing;
   const int vi_k = small ? 24 + (shard ? 4 : 0) + wide * 2 + ks16
                          : (shard ? 16 + local * 4 + wide * 2 + ks16 : local * 8 + wide * 4 + timing * 2 + ks16);
+  // One tower per gradient workgroup (`ppo_update_split_kernel`): several gradient workgroups of one process, switch on,
+  // and -- checked per launch below -- 2 nblk + 1 + 2 n_slices workgroups co-resident; otherwise the form above, unchanged.
+  // [wide * 4 + timing * 2 + ks16]; its own caches of the LDS attribute and the occupancy.
+  static const KernelT split_kernels[8] = {
+      ppo_update_split_kernel<UPD_NPT, false, 8>,      ppo_update_split_kernel<UPD_NPT, false, 16>,
+      ppo_update_split_kernel<UPD_NPT, true, 8>,       ppo_update_split_kernel<UPD_NPT, true, 16>,
+      ppo_update_split_kernel<UPD_NPT_WIDE, false, 8>, ppo_update_split_kernel<UPD_NPT_WIDE, false, 16>,
+      ppo_update_split_kernel<UPD_NPT_WIDE, true, 8>,  ppo_update_split_kernel<UPD_NPT_WIDE, true, 16>};
+  const bool want_split = g_upd_tower_split && shard == nullptr && nblk >= 2;
+  const int vi_s = wide * 4 + timing * 2 + ks16;
   const KernelT kernel = kernels[vi_k];
   static size_t attr_bytes[32] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (bytes > attr_bytes[vi_k]) {
@@ -6386,9 +6533,40 @@ static int ppo_update_launch(const ia_policy_desc* d, float* params, float* para
     // 1024-row minibatch -- as long as a whole gradient step, so the chain kept waiting 1-2 us per step for
     // it; two slices + merge take ~14 us and the ring runs ahead again.)
     const int n_slices = (batch_global > UPD_SLICE && total < (1ll << 31)) ? cdiv(batch_global, UPD_SLICE) : 0;
-    const bool pack = g_upd_xcd_pack && nblk > 1 && nblk + 1 + n_slices <= 32;
-    const int grid = (nblk + 1 + n_slices) * (pack ? 8 : 1);
-    {
+    bool pack = g_upd_xcd_pack && nblk > 1 && nblk + 1 + n_slices <= 32;
+    int grid = (nblk + 1 + n_slices) * (pack ? 8 : 1);
+    KernelT launch_kernel = kernel;
+    if (want_split) {   // the same residency test for the wider grid; no room -> the two-tower form (and ITS test) below
+      static int s_dev_cus = 0, s_per_cu[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+      static size_t s_per_cu_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s_attr_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (bytes > s_attr_bytes[vi_s]) {
+        const int rc = set_lds(split_kernels[vi_s], bytes);
+        if (rc) return rc;
+        s_attr_bytes[vi_s] = bytes;
+      }
+      if (s_dev_cus == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&s_dev_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+          return IA_ERR_ARG;
+      }
+      const int cu_count = g_upd_assume_cus > 0 ? g_upd_assume_cus : s_dev_cus;
+      if (s_per_cu[vi_s] < 0 || s_per_cu_bytes[vi_s] != bytes) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(split_kernels[vi_s]), 512,
+                                                         bytes) != hipSuccess)
+          return IA_ERR_ARG;
+        s_per_cu[vi_s] = nb;
+        s_per_cu_bytes[vi_s] = bytes;
+      }
+      const int split_grid = 2 * nblk + 1 + 2 * n_slices;   // (two workgroups per statistics slice: even / odd steps)
+      if ((long long)s_per_cu[vi_s] * cu_count >= split_grid) {
+        launch_kernel = split_kernels[vi_s];
+        grid = split_grid;
+        pack = false;   // (packing onto one XCD does not apply: twice the workgroups, and they are meant to spread)
+      }
+    }
+    if (launch_kernel == kernel) {
       // The grid barriers inside need every workgroup resident at once. A plain launch performs no such check
       // (and a cooperative launch costs +15-19 us per launch, MI355X_MICROARCH.md "coop-launch"), so the same
       // test is made here: workgroups per CU by the occupancy query (LDS-bound: one) times the CU count.
@@ -6421,7 +6599,7 @@ static int ppo_update_launch(const ia_policy_desc* d, float* params, float* para
     } else {
       memset(&sa, 0, sizeof(sa));
     }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), bytes, st, *d, params, params_t, exp_avg,
+    hipLaunchKernelGGL(launch_kernel, dim3(grid), dim3(512), bytes, st, *d, params, params_t, exp_avg,
                        exp_avg_sq, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp, advantages,
                        returns, perm, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, max_grad_norm,
                        (float)beta1, (float)beta2, adam_eps, ws, nblk, n_slices, stats, sch, pack ? 1 : 0, g_tstamp, sa);

@@ -529,6 +529,9 @@ class PPO(OnPolicyAlgorithm):
         n_upd = int(L.load().ia_ppo_update_ws_floats(C.byref(p.desc), min(self.batch_size, total))) if p.fused else 0
         # persistent whole-update kernel (hidden = 32); None -> one ia_ppo_epoch call per epoch
         self._upd_ws = th.zeros(n_upd, device=self.device) if n_upd > 0 else None
+        # ... with one tower per gradient workgroup, two workgroups per row block, where several row blocks' worth fit the
+        # device (a library-wide switch; bit-identical results). `IA_PPO_TOWER_SPLIT=0`: one per row block
+        L.load().ia_ppo_update_tower_split(1 if os.environ.get("IA_PPO_TOWER_SPLIT", "1") != "0" else 0)
         self.dp = None  # set by the trainer for data-parallel runs (imitation_amd.distributed.DataParallel)
         # When True, `train()` only ENQUEUES the update and returns; the caller overlaps other GPU
         # work with it and later calls `finalize_train()` (one D2H of the statistics + logging).

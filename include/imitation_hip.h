@@ -749,6 +749,11 @@ int ia_ppo_update_xcd_pack(int on);
  * barriers) would not all be resident at once: occupancy query x compute units < grid. Tests: pretend the
  * device has n compute units (0 = ask the device). */
 int ia_ppo_update_assume_cus(int n);
+/* ia_ppo_update_tower_split(1): with several gradient workgroups in one process (minibatches beyond 64 rows, not the
+ * row-sharded form) every 64-row block gets TWO gradient workgroups, one per tower of the policy, on compute units of
+ * their own, and every statistics slice two (even / odd steps) -- 2 nblk + 1 + 2 slices workgroups, all co-resident (same occupancy x compute-unit test; when they do not
+ * fit, the call runs the form of 0). Same workspace, bit-identical results. 0: one workgroup per row block. */
+int ia_ppo_update_tower_split(int on);
 int ia_ppo_update(const ia_policy_desc* d, float* params, float* params_t, float* norm_mean, float* norm_var,
                   int32_t* norm_count, int update_norm, const float* obs, const float* actions, const float* old_logp,
                   const float* advantages, const float* returns, const int64_t* perm, int n_epochs, int T, int n_envs,
