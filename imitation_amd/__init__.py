@@ -22,11 +22,13 @@ from imitation_amd.adversarial.common import AdversarialTrainer, compute_train_s
 from imitation_amd.adversarial.gail import GAIL, RewardNetFromDiscriminatorLogit  # noqa: F401
 from imitation_amd.adversarial.airl import AIRL  # noqa: F401
 from imitation_amd.density import DensityAlgorithm, DensityType  # noqa: F401
-from imitation_amd import (bc, checkpoint, cnn_policy, dagger, density, mce_irl, modules, ops,  # noqa: F401
-                           preference_comparisons, rollout, serialize)
+from imitation_amd import (bc, checkpoint, cnn_policy, dagger, density, dqn, mce_irl, modules, ops,  # noqa: F401
+                           preference_comparisons, rollout, serialize, sqil)
 from imitation_amd.dagger import (DAggerTrainer, ExponentialBetaSchedule, InteractiveTrajectoryCollector,  # noqa: F401
                                   LinearBetaSchedule, NeedsDemosException, SimpleDAggerTrainer)
 from imitation_amd.mce_irl import MCEIRL, TabularPolicy  # noqa: F401
+from imitation_amd.dqn import DQN, DQNPolicy, QNetwork  # noqa: F401
+from imitation_amd.sqil import SQIL, SQILReplayBuffer  # noqa: F401
 
 
 def configure_logger(folder=None, format_strs=None):

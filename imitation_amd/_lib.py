@@ -258,6 +258,12 @@ _SIGS = {
     "ia_mce_forward": ([_P, _P, _P, _I, _I, _I, _D, _P, _P, _P, _P], C.c_int),
     "ia_mce_weights": ([_P, _P, _I, _P, _P, _P], C.c_int),
     "ia_mce_norms": ([_P, _P, _L, _P, _P], C.c_int),
+    "ia_dqn_update_ok": ([_I, _I, _I, _I], C.c_int),
+    "ia_dqn_update": ([_I] * 6 + [_P] * 15 + [_F, _F, _D, _D, _F] + [_P, _P, _P, _P], C.c_int),
+    "ia_dqn_adam_step": ([_P, _P, _P, _P, _L, _D, _D, _F, _F, _F, _F, _P], C.c_int),
+    "ia_dqn_q_values": ([_I, _I, _I, _P, _P, _I, _P, _P, _P], C.c_int),
+    "ia_dqn_td_loss": ([_P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P], C.c_int),
+    "ia_polyak_update": ([_P, _P, _L, _F, _P], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

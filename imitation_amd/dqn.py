@@ -1,0 +1,687 @@
+"""What SQIL needs of stable-baselines3's DQN (`algorithms/sqil.py:12-19,77-83`): `DQN`, `DQNPolicy` ("MlpPolicy"),
+`QNetwork`, SB3's `ReplayBuffer` and the off-policy loop -- a restatement of stable-baselines3 2.2.x from its documented
+behaviour ([SB3 dqn/dqn.py, dqn/policies.py, common/off_policy_algorithm.py, common/buffers.py]).
+
+Layout, as everywhere in this package: every index decision (ring position, sampled rows, exploration
+coin, random actions) is made on the host with SB3's own draw sequence from NumPy's GLOBAL stream; the learner ring and
+the expert table live in device memory and rows never come back -- a step uploads its transition and reads back the
+arg-max, a `train` call uploads ONE int64 index array for all its gradient steps and reads back one block of statistics.
+
+The update itself is `ia_dqn_update` (csrc/dqn.hip): all gradient steps of a `train` call in one launch of one workgroup,
+for `net_arch=[H, H]`, H in {32, 64}, ReLU, D <= 64, A <= 16, batch <= 256. Every other Q-net runs the same update from
+the general kernels (`ia_gather_rows`, `ia_mlp_forward` twice, `ia_dqn_td_loss`, `ia_mlp_backward` + `ia_reduce_partials`,
+`ia_clip_grad_norm`, `ia_dqn_adam_step`); `IA_DQN_FUSED=0` in the environment forces that path (tests, tools).
+"""
+from __future__ import annotations
+
+import collections
+import copy
+import ctypes as C
+import os
+import sys
+import time
+import warnings
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch as th
+from torch import nn
+
+from imitation_amd import _lib as L
+from imitation_amd import logger as imit_logger
+from imitation_amd import spaces
+from imitation_amd.networks import require_device
+from imitation_amd.policies import FlattenExtractor
+from imitation_amd.ppo import _CallbackList, _NullCallback, _schedule, set_random_seed
+
+
+def fused_enabled() -> bool:
+    """`IA_DQN_FUSED=0` sends every shape down the general path."""
+    return os.environ.get("IA_DQN_FUSED", "1") != "0"
+
+
+def get_linear_fn(start: float, end: float, end_fraction: float):
+    """[SB3 utils.get_linear_fn]: from `start` to `end` while `1 - progress_remaining` goes from 0 to `end_fraction`."""
+
+    def func(progress_remaining: float) -> float:
+        if (1 - progress_remaining) > end_fraction:
+            return end
+        return start + (1 - progress_remaining) * (end - start) / end_fraction
+
+    return func
+
+
+class ReplayBufferSamples(NamedTuple):
+    """[SB3 type_aliases.ReplayBufferSamples]"""
+    observations: th.Tensor
+    actions: th.Tensor
+    next_observations: th.Tensor
+    dones: th.Tensor
+    rewards: th.Tensor
+
+
+class ReplayIndex:
+    """The index logic of [SB3 buffers.ReplayBuffer], host only (no tensor, no GPU): a ring of
+    `max(buffer_size // n_envs, 1)` positions of `n_envs` rows each; `add` returns the position it wrote and wraps;
+    `sample` makes SB3's two draws from NumPy's GLOBAL stream (`np.random.randint(0, upper, size=b)`, then
+    `np.random.randint(0, high=n_envs, size=(b,))`); the row of (position, env) in a flat table is
+    `position * n_envs + env`."""
+
+    def __init__(self, buffer_size: int, n_envs: int = 1):
+        self.n_envs = int(n_envs)
+        self.buffer_size = max(int(buffer_size) // self.n_envs, 1)
+        self.pos = 0
+        self.full = False
+
+    def size(self) -> int:
+        return self.buffer_size if self.full else self.pos
+
+    def add(self) -> int:
+        at = self.pos
+        self.pos += 1
+        if self.pos == self.buffer_size:
+            self.full = True
+            self.pos = 0
+        return at
+
+    def fill(self) -> None:
+        """The state after `buffer_size` adds (the expert table: one add per demonstration)."""
+        self.pos, self.full = 0, True
+
+    def sample(self, batch_size: int) -> Tuple[np.ndarray, np.ndarray]:
+        upper_bound = self.buffer_size if self.full else self.pos
+        batch_inds = np.random.randint(0, upper_bound, size=batch_size)
+        env_indices = np.random.randint(0, high=self.n_envs, size=(len(batch_inds),))
+        return batch_inds, env_indices
+
+    def rows(self, batch_inds: np.ndarray, env_indices: np.ndarray) -> np.ndarray:
+        return batch_inds.astype(np.int64) * self.n_envs + env_indices.astype(np.int64)
+
+
+class _Table:
+    """Flat device table of transitions: obs / next_obs [N, D] float32, action int64 [N], reward, done float32 [N]."""
+
+    def __init__(self, rows: int, obs_dim: int, device):
+        self.rows, self.obs_dim = int(rows), int(obs_dim)
+        self.obs = th.zeros(self.rows, obs_dim, device=device)
+        self.next_obs = th.zeros(self.rows, obs_dim, device=device)
+        self.action = th.zeros(self.rows, dtype=th.int64, device=device)
+        self.reward = th.zeros(self.rows, device=device)
+        self.done = th.zeros(self.rows, device=device)
+
+    def write(self, lo: int, obs, next_obs, action, reward, done) -> None:
+        n = len(obs)
+        for dst, src, dtype, shape in ((self.obs, obs, np.float32, (n, -1)), (self.next_obs, next_obs, np.float32, (n, -1)),
+                                       (self.action, action, np.int64, (n,)), (self.reward, reward, np.float32, (n,)),
+                                       (self.done, done, np.float32, (n,))):
+            dst[lo:lo + n].copy_(th.from_numpy(np.array(src, dtype).reshape(shape)))
+
+
+def _device(device) -> th.device:
+    return th.device("cuda" if device == "auto" else device)
+
+
+class ReplayBuffer:
+    """[SB3 buffers.ReplayBuffer] for flat Box observations and Discrete actions, its rows in device memory.
+    `handle_timeout_termination`: a `done` that is a time-limit truncation does not cut the bootstrap (the product
+    `done * (1 - timeout)` SB3 forms when sampling is formed when the row is stored)."""
+
+    def __init__(self, buffer_size: int, observation_space, action_space, device="auto", n_envs: int = 1,
+                 optimize_memory_usage: bool = False, handle_timeout_termination: bool = True):
+        if optimize_memory_usage:
+            raise NotImplementedError("optimize_memory_usage is not implemented")
+        if not isinstance(observation_space, spaces.Box) or not isinstance(action_space, spaces.Discrete):
+            raise NotImplementedError("the replay buffer holds flat Box observations and Discrete actions")
+        self.observation_space, self.action_space = observation_space, action_space
+        self.obs_dim = int(np.prod(observation_space.shape))
+        self.device = _device(device)
+        self.n_envs = int(n_envs)
+        self.index = ReplayIndex(buffer_size, n_envs)
+        self.buffer_size = self.index.buffer_size
+        self.handle_timeout_termination = handle_timeout_termination
+        self.table = _Table(self.buffer_size * self.n_envs, self.obs_dim, self.device)
+
+    @property
+    def pos(self) -> int:
+        return self.index.pos
+
+    @property
+    def full(self) -> bool:
+        return self.index.full
+
+    def size(self) -> int:
+        return self.index.size()
+
+    def add(self, obs, next_obs, action, reward, done, infos) -> None:
+        done = np.asarray(done, np.float32).reshape(-1)
+        if self.handle_timeout_termination:
+            timeouts = np.array([info.get("TimeLimit.truncated", False) for info in infos], np.float32)
+            done = done * (1 - timeouts)
+        reward = np.array(np.broadcast_to(np.asarray(reward, np.float32), (self.n_envs,)))
+        at = self.index.add()
+        self.table.write(at * self.n_envs, obs, next_obs, action, reward, done)
+
+    def sample_rows(self, batch_size: int) -> Tuple[np.ndarray, int]:
+        """The flat rows of one minibatch and how many of them (the first) index the learner ring: all here."""
+        return self.index.rows(*self.index.sample(batch_size)), batch_size
+
+    def expert_table(self) -> Optional[_Table]:
+        return None
+
+    def _gather(self, table: _Table, rows: np.ndarray) -> ReplayBufferSamples:
+        idx = th.from_numpy(rows).to(self.device)
+        return ReplayBufferSamples(table.obs[idx], table.action[idx].reshape(-1, 1), table.next_obs[idx],
+                                   table.done[idx].reshape(-1, 1), table.reward[idx].reshape(-1, 1))
+
+    def sample(self, batch_size: int, env=None) -> ReplayBufferSamples:
+        """[SB3 ReplayBuffer.sample] as tensors (the training loop itself passes `sample_rows` to the kernels)."""
+        if env is not None:
+            raise NotImplementedError("VecNormalize is not implemented")
+        rows, _ = ReplayBuffer.sample_rows(self, batch_size)
+        return self._gather(self.table, rows)
+
+
+class QNetwork:
+    """[SB3 dqn.policies.QNetwork]: `create_mlp(features_dim, n_actions, net_arch, activation_fn)` over the flattened
+    observation; parameters as one flat device vector in torch's `parameters()` order."""
+
+    def __init__(self, observation_space, action_space, net_arch: List[int], activation_fn=nn.ReLU):
+        if not isinstance(action_space, spaces.Discrete):
+            raise NotImplementedError("DQN needs a Discrete action space")
+        if not isinstance(observation_space, spaces.Box):
+            raise NotImplementedError("the Q-network takes flat Box observations")
+        if activation_fn not in (nn.ReLU, nn.Tanh):
+            raise NotImplementedError(f"activation {activation_fn} is not implemented on the HIP path")
+        self.observation_space, self.action_space = observation_space, action_space
+        self.obs_dim, self.n_actions = int(np.prod(observation_space.shape)), int(action_space.n)
+        self.net_arch, self.activation_fn = [int(h) for h in net_arch], activation_fn
+        self.act = L.ACT_RELU if activation_fn is nn.ReLU else L.ACT_TANH
+        self.dims = [self.obs_dim] + self.net_arch + [self.n_actions]
+        if len(self.dims) - 1 > L.IA_MAX_LAYERS:
+            raise NotImplementedError(f"at most {L.IA_MAX_LAYERS} layers")
+        # CPU modules give torch's default initialisation AND its consumption of the global generator
+        layers: List[nn.Module] = []
+        for i in range(len(self.dims) - 1):
+            layers.append(nn.Linear(self.dims[i], self.dims[i + 1]))
+            if i < len(self.dims) - 2:
+                layers.append(activation_fn())
+        seq = nn.Sequential(*layers)
+        self._names = [(k, tuple(v.shape)) for k, v in seq.state_dict().items()]
+        self._flat = th.cat([p.detach().reshape(-1) for p in seq.parameters()]).contiguous()
+        self.desc = L.mlp_desc(self.dims, self.act)
+
+    @property
+    def device(self) -> th.device:
+        return self._flat.device
+
+    def to(self, device):
+        self._flat = self._flat.to(device).contiguous()
+        return self
+
+    def fused_shape(self) -> bool:
+        return (len(self.net_arch) == 2 and self.net_arch[0] == self.net_arch[1] and self.net_arch[0] in (32, 64)
+                and self.act == L.ACT_RELU and self.obs_dim <= 64 and self.n_actions <= 16)
+
+    def parameters(self):
+        off = 0
+        for _, shape in self._names:
+            n = int(np.prod(shape))
+            yield self._flat[off:off + n].view(shape)
+            off += n
+
+    def state_dict(self) -> Dict[str, th.Tensor]:
+        return {f"q_net.{k}": p for (k, _), p in zip(self._names, self.parameters())}
+
+    def load_state_dict(self, sd) -> None:
+        for (k, shape), p in zip(self._names, self.parameters()):
+            p.copy_(th.as_tensor(sd[f"q_net.{k}"]).reshape(shape))
+
+    def q_values(self, obs_dev: th.Tensor) -> Tuple[th.Tensor, Optional[th.Tensor]]:
+        """Q [n, A] on device rows `obs_dev[n, D]`; with it the first arg-max per row where the act kernel covers the net
+        (None otherwise: the caller takes it from Q)."""
+        require_device(self.device)
+        n = obs_dev.shape[0]
+        q = th.empty(n, self.n_actions, device=self.device)
+        if self.fused_shape() and fused_enabled():
+            am = th.empty(n, dtype=th.int64, device=self.device)
+            L.call("ia_dqn_q_values", self.obs_dim, self.net_arch[0], self.n_actions, L.ptr(self._flat), L.ptr(obs_dev), n,
+                   L.ptr(q), L.ptr(am), L.stream())
+            return q, am
+        hidden = th.empty(max(1, n * sum(self.net_arch)), device=self.device)
+        L.call("ia_mlp_forward", C.byref(self.desc), L.ptr(self._flat), L.ptr(obs_dev), self.obs_dim, n, L.ptr(hidden),
+               L.ptr(q), L.ACT_NONE, L.stream())
+        return q, None
+
+
+class DQNPolicy:
+    """[SB3 dqn.policies.DQNPolicy]: `q_net`, then a separately initialised `q_net_target` that loads the online
+    net's state, then Adam over the online parameters."""
+
+    def __init__(self, observation_space, action_space, lr_schedule, net_arch: Optional[List[int]] = None,
+                 activation_fn=nn.ReLU, features_extractor_class=FlattenExtractor, features_extractor_kwargs=None,
+                 normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs=None):
+        if features_extractor_class is not FlattenExtractor:
+            raise NotImplementedError("only the flatten extractor (MlpPolicy) is implemented")
+        if optimizer_class is not th.optim.Adam:
+            raise NotImplementedError("only torch.optim.Adam is implemented")
+        self.observation_space, self.action_space = observation_space, action_space
+        self.net_arch = [64, 64] if net_arch is None else list(net_arch)
+        self.activation_fn = activation_fn
+        self.optimizer_kwargs = dict(optimizer_kwargs or {})
+        unknown = set(self.optimizer_kwargs) - {"betas", "eps", "weight_decay"}
+        if unknown:
+            raise NotImplementedError(f"optimizer_kwargs {sorted(unknown)} are not implemented")
+        self.q_net = QNetwork(observation_space, action_space, self.net_arch, activation_fn)
+        self.q_net_target = QNetwork(observation_space, action_space, self.net_arch, activation_fn)
+        self.q_net_target._flat.copy_(self.q_net._flat)
+        self.lr = float(lr_schedule(1))
+        self.betas = tuple(self.optimizer_kwargs.get("betas", (0.9, 0.999)))
+        self.eps = float(self.optimizer_kwargs.get("eps", 1e-8))
+        self.weight_decay = float(self.optimizer_kwargs.get("weight_decay", 0.0))
+        self.exp_avg = th.zeros_like(self.q_net._flat)
+        self.exp_avg_sq = th.zeros_like(self.q_net._flat)
+        self.adam_steps = 0
+        self.training = True
+        self._ws: Dict[Any, Any] = {}
+
+    @property
+    def device(self) -> th.device:
+        return self.q_net.device
+
+    def to(self, device):
+        self.q_net.to(device)
+        self.q_net_target.to(device)
+        self.exp_avg, self.exp_avg_sq = self.exp_avg.to(device), self.exp_avg_sq.to(device)
+        self._ws = {}
+        return self
+
+    def set_training_mode(self, mode: bool) -> None:
+        self.training = mode
+
+    def parameters(self):
+        yield from self.q_net.parameters()
+        yield from self.q_net_target.parameters()
+
+    def state_dict(self) -> Dict[str, th.Tensor]:
+        out = {f"q_net.{k}": v for k, v in self.q_net.state_dict().items()}
+        out.update({f"q_net_target.{k}": v for k, v in self.q_net_target.state_dict().items()})
+        return out
+
+    def load_state_dict(self, sd) -> None:
+        self.q_net.load_state_dict({k[len("q_net."):]: v for k, v in sd.items() if k.startswith("q_net.")})
+        self.q_net_target.load_state_dict(
+            {k[len("q_net_target."):]: v for k, v in sd.items() if k.startswith("q_net_target.")})
+
+    def q_values(self, observation: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """Q and the greedy action of host observations (one upload, one read-back)."""
+        obs = np.ascontiguousarray(observation, np.float32).reshape(-1, self.q_net.obs_dim)
+        q, am = self.q_net.q_values(th.from_numpy(obs).to(self.device))
+        if am is None:
+            qh = q.cpu().numpy()
+            return qh, qh.argmax(axis=1).astype(np.int64)
+        both = th.cat([q.reshape(-1), am.to(th.float32)]).cpu().numpy()   # (action indices < 2^24: exact as floats)
+        n = len(obs)
+        return both[:n * self.q_net.n_actions].reshape(n, -1), both[n * self.q_net.n_actions:].astype(np.int64)
+
+    def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
+        """[SB3 BasePolicy.predict]: the greedy action (`_predict` is the arg-max whatever `deterministic` says)."""
+        self.set_training_mode(False)
+        observation = np.asarray(observation)
+        vectorized = observation.shape != tuple(self.observation_space.shape)
+        _, actions = self.q_values(observation)
+        if not vectorized:
+            return actions[0], state
+        return actions, state
+
+    def polyak_update(self, tau: float) -> None:
+        """[SB3 utils.polyak_update] of the target from the online parameters."""
+        L.call("ia_polyak_update", L.ptr(self.q_net._flat), L.ptr(self.q_net_target._flat), self.q_net._flat.numel(),
+               float(tau), L.stream())
+
+    # ---- the update -------------------------------------------------------------------------------------------------
+    # Routing by measured cost (tools/sqil_step_bench.py --sweep, H = 64, microseconds per gradient step inside a 16-step
+    # call): the one-workgroup kernel walks the batch in 16-row groups, 27 + 15.6 per group at D = 4 and 35 + 25.3 per group
+    # at D = 64 (taken as linear in D in between); the general path's launches cost 104 - 113 whatever the batch. A shape
+    # whose estimate exceeds the limit takes the general path (D = 4: batches above 64; D = 64: above 32 -- the largest
+    # batches at which the kernel was measured ahead; at the next group the two paths tie).
+    FUSED_COST_LIMIT_US = 100.0
+
+    def fused_cost_us(self, batch_size: int) -> float:
+        D = self.q_net.obs_dim
+        return 26.5 + D / 8.0 + -(-int(batch_size) // 16) * (15.0 + 0.16 * D)
+
+    def fused_ok(self, batch_size: int) -> bool:
+        q = self.q_net
+        return (fused_enabled() and q.fused_shape() and self.weight_decay == 0.0 and
+                self.fused_cost_us(batch_size) <= self.FUSED_COST_LIMIT_US and
+                bool(L.load().ia_dqn_update_ok(q.obs_dim, q.net_arch[0], q.n_actions, int(batch_size))))
+
+    def _adam_scalars(self, lr: float, n_steps: int) -> np.ndarray:
+        b1, b2 = self.betas
+        out = np.empty((n_steps, 2), np.float32)
+        for s in range(n_steps):
+            t = self.adam_steps + s + 1
+            out[s, 0] = lr / (1.0 - b1 ** t)
+            out[s, 1] = (1.0 - b2 ** t) ** 0.5
+        return out
+
+    def update_fused(self, ring: _Table, expert: Optional[_Table], idx_dev: th.Tensor, n_new: int, n_steps: int,
+                     batch_size: int, gamma: float, max_grad_norm: float, lr: float, stats: th.Tensor,
+                     grad_out: Optional[th.Tensor] = None) -> None:
+        """`n_steps` gradient steps in one launch (`ia_dqn_update`); `idx_dev` int64 [n_steps, batch_size]."""
+        q = self.q_net
+        scal = np.ascontiguousarray(self._adam_scalars(lr, n_steps))
+        e = expert
+        rc = L.load().ia_dqn_update(
+            q.obs_dim, q.net_arch[0], q.n_actions, int(batch_size), int(n_new), int(n_steps), L.ptr(q._flat),
+            L.ptr(self.q_net_target._flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(ring.obs),
+            L.ptr(ring.next_obs), L.ptr(ring.action), L.ptr(ring.reward), L.ptr(ring.done),
+            None if e is None else L.ptr(e.obs), None if e is None else L.ptr(e.next_obs),
+            None if e is None else L.ptr(e.action), None if e is None else L.ptr(e.reward),
+            None if e is None else L.ptr(e.done), L.ptr(idx_dev), float(gamma), float(max_grad_norm), float(self.betas[0]),
+            float(self.betas[1]), self.eps, scal.ctypes.data, L.ptr(stats), L.ptr(grad_out), L.stream())
+        L.check(rc, "ia_dqn_update")
+        self.adam_steps += n_steps
+
+    def _general_ws(self, B: int):
+        key = ("general", B)
+        if key not in self._ws:
+            q, dev = self.q_net, self.device
+            hid = max(1, B * sum(q.net_arch))
+            n = q._flat.numel()
+            splits = max(1, min(64, B // 256))
+            self._ws[key] = dict(
+                obs=th.empty(B, q.obs_dim, device=dev), nxt=th.empty(B, q.obs_dim, device=dev),
+                act=th.empty(B, dtype=th.int64, device=dev), rew=th.empty(B, device=dev), done=th.empty(B, device=dev),
+                hidden=th.empty(hid, device=dev), hidden_t=th.empty(hid, device=dev), dhidden=th.empty(hid, device=dev),
+                q=th.empty(B, q.n_actions, device=dev), qt=th.empty(B, q.n_actions, device=dev),
+                dq=th.empty(B, q.n_actions, device=dev), terms=th.empty(B, device=dev), splits=splits,
+                partials=th.empty(splits, n, device=dev), grads=th.empty(n, device=dev))
+        return self._ws[key]
+
+    def update_general(self, ring: _Table, expert: Optional[_Table], idx_dev: th.Tensor, n_new: int, n_steps: int,
+                       batch_size: int, gamma: float, max_grad_norm: float, lr: float, stats: th.Tensor,
+                       grad_out: Optional[th.Tensor] = None) -> None:
+        """The same steps from the general kernels, one launch sequence per step."""
+        q, B, st = self.q_net, int(batch_size), L.stream()
+        w = self._general_ws(B)
+        scal = self._adam_scalars(lr, n_steps)
+        n = q._flat.numel()
+        D = q.obs_dim
+        idx_ptr, stats_ptr = idx_dev.data_ptr(), stats.data_ptr()
+        for s in range(n_steps):
+            for table, lo, cnt in ((ring, 0, n_new), (expert, n_new, B - n_new)):
+                if cnt == 0:
+                    continue
+                ip = idx_ptr + 8 * (s * B + lo)
+                L.call("ia_gather_rows", L.ptr(table.obs), ip, cnt, D, w["obs"].data_ptr() + 4 * lo * D, st)
+                L.call("ia_gather_rows", L.ptr(table.next_obs), ip, cnt, D, w["nxt"].data_ptr() + 4 * lo * D, st)
+                # (int64 actions travel as pairs of 32-bit words: the gather moves bits)
+                L.call("ia_gather_rows", L.ptr(table.action), ip, cnt, 2, w["act"].data_ptr() + 8 * lo, st)
+                L.call("ia_gather_rows", L.ptr(table.reward), ip, cnt, 1, w["rew"].data_ptr() + 4 * lo, st)
+                L.call("ia_gather_rows", L.ptr(table.done), ip, cnt, 1, w["done"].data_ptr() + 4 * lo, st)
+            L.call("ia_mlp_forward", C.byref(q.desc), L.ptr(q._flat), L.ptr(w["obs"]), D, B, L.ptr(w["hidden"]),
+                   L.ptr(w["q"]), L.ACT_NONE, st)
+            L.call("ia_mlp_forward", C.byref(q.desc), L.ptr(self.q_net_target._flat), L.ptr(w["nxt"]), D, B,
+                   L.ptr(w["hidden_t"]), L.ptr(w["qt"]), L.ACT_NONE, st)
+            L.call("ia_dqn_td_loss", L.ptr(w["q"]), L.ptr(w["qt"]), L.ptr(w["act"]), L.ptr(w["rew"]), L.ptr(w["done"]), B,
+                   q.n_actions, float(gamma), L.ptr(w["dq"]), L.ptr(w["terms"]), stats_ptr + 8 * s, st)
+            L.call("ia_mlp_backward", C.byref(q.desc), L.ptr(q._flat), L.ptr(w["obs"]), D, B, L.ptr(w["hidden"]),
+                   L.ptr(w["dq"]), L.ptr(w["dhidden"]), L.ptr(w["partials"]), w["splits"], None, st)
+            L.call("ia_reduce_partials", L.ptr(w["partials"]), w["splits"], n, 1.0, 0, L.ptr(w["grads"]), st)
+            L.call("ia_clip_grad_norm", L.ptr(w["grads"]), n, float(max_grad_norm), stats_ptr + 8 * s + 4, None, st)
+            L.call("ia_dqn_adam_step", L.ptr(q._flat), L.ptr(w["grads"]), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), n,
+                   float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay, float(scal[s, 0]),
+                   float(scal[s, 1]), st)
+        if grad_out is not None:
+            grad_out.copy_(w["grads"])
+        self.adam_steps += n_steps
+
+    def update(self, ring: _Table, expert: Optional[_Table], idx_dev: th.Tensor, n_new: int, n_steps: int,
+               batch_size: int, gamma: float, max_grad_norm: float, lr: float, stats: th.Tensor,
+               grad_out: Optional[th.Tensor] = None) -> None:
+        """The fused launch where `fused_ok(batch_size)`, else the general path."""
+        fn = self.update_fused if self.fused_ok(batch_size) else self.update_general
+        fn(ring, expert, idx_dev, n_new, n_steps, batch_size, gamma, max_grad_norm, lr, stats, grad_out)
+
+
+MlpPolicy = DQNPolicy
+
+
+class OffPolicyAlgorithm:
+    """Marker base, as `ppo.OnPolicyAlgorithm`."""
+
+
+class DQN(OffPolicyAlgorithm):
+    """[SB3 dqn.DQN] with `train_freq` in steps."""
+
+    policy_aliases = {"MlpPolicy": DQNPolicy}
+
+    def __init__(self, policy, env, learning_rate=1e-4, buffer_size: int = 1_000_000, learning_starts: int = 50_000,
+                 batch_size: int = 32, tau: float = 1.0, gamma: float = 0.99, train_freq=4, gradient_steps: int = 1,
+                 replay_buffer_class=None, replay_buffer_kwargs: Optional[Dict[str, Any]] = None,
+                 optimize_memory_usage: bool = False, target_update_interval: int = 10_000,
+                 exploration_fraction: float = 0.1, exploration_initial_eps: float = 1.0,
+                 exploration_final_eps: float = 0.05, max_grad_norm: float = 10, stats_window_size: int = 100,
+                 tensorboard_log=None, policy_kwargs: Optional[Dict[str, Any]] = None, verbose: int = 0,
+                 seed: Optional[int] = None, device="auto", _init_setup_model: bool = True):
+        if isinstance(policy, str):
+            if policy not in self.policy_aliases:
+                raise NotImplementedError(f"policy {policy!r}: only 'MlpPolicy' is implemented for DQN")
+            policy = self.policy_aliases[policy]
+        if isinstance(train_freq, tuple):
+            if len(train_freq) != 2 or train_freq[1] != "step":
+                raise NotImplementedError("train_freq is counted in steps")
+            train_freq = train_freq[0]
+        if tensorboard_log is not None:
+            raise NotImplementedError("tensorboard logging is not implemented")
+        self.policy_class = policy
+        self.policy_kwargs = dict(policy_kwargs or {})
+        self.device = _device(device)
+        self.learning_rate, self.buffer_size, self.learning_starts = learning_rate, buffer_size, learning_starts
+        self.batch_size, self.tau, self.gamma = batch_size, tau, gamma
+        self.train_freq, self.gradient_steps = int(train_freq), gradient_steps
+        self.replay_buffer_class = replay_buffer_class
+        self.replay_buffer_kwargs = dict(replay_buffer_kwargs or {})
+        self.optimize_memory_usage = optimize_memory_usage
+        self.target_update_interval = target_update_interval
+        self.exploration_initial_eps, self.exploration_final_eps = exploration_initial_eps, exploration_final_eps
+        self.exploration_fraction = exploration_fraction
+        self.max_grad_norm, self.seed, self.verbose = max_grad_norm, seed, verbose
+        self._n_calls = 0
+        self.exploration_rate = 0.0   # [SB3 dqn.py]: zero until the first `_on_step`
+        self.num_timesteps = 0
+        self._total_timesteps = 0
+        self._num_timesteps_at_start = 0
+        self._n_updates = 0
+        self._episode_num = 0
+        self._current_progress_remaining = 1.0
+        self._last_obs = None
+        self._last_episode_starts = None
+        self._stats_window_size = stats_window_size
+        self.ep_info_buffer = None
+        self._logger: Optional[imit_logger.Logger] = None
+        self._custom_logger = False
+        self.start_time = 0
+        self.env = env
+        self.policy: Optional[DQNPolicy] = None
+        self.replay_buffer: Optional[ReplayBuffer] = None
+        self.last_action_branch: Optional[str] = None   # "warmup" / "explore" / "greedy" of the latest `_sample_action`
+        if env is not None:
+            self.observation_space, self.action_space, self.n_envs = env.observation_space, env.action_space, env.num_envs
+        if _init_setup_model:
+            self._setup_model()
+
+    def _setup_model(self) -> None:
+        self.lr_schedule = _schedule(self.learning_rate)
+        if self.seed is not None:
+            set_random_seed(self.seed)
+            self.action_space.seed(self.seed)
+            if self.env is not None:
+                self.env.seed(self.seed)
+        if self.replay_buffer_class is None:
+            self.replay_buffer_class = ReplayBuffer
+        if self.replay_buffer is None:
+            self.replay_buffer = self.replay_buffer_class(
+                self.buffer_size, self.observation_space, self.action_space, device=self.device, n_envs=self.n_envs,
+                optimize_memory_usage=self.optimize_memory_usage, **self.replay_buffer_kwargs)
+        self.policy = self.policy_class(self.observation_space, self.action_space, self.lr_schedule,
+                                        **self.policy_kwargs).to(self.device)
+        self.q_net, self.q_net_target = self.policy.q_net, self.policy.q_net_target
+        self.exploration_schedule = get_linear_fn(self.exploration_initial_eps, self.exploration_final_eps,
+                                                  self.exploration_fraction)
+        if self.n_envs > 1 and self.n_envs > self.target_update_interval:
+            warnings.warn("The number of environments used is greater than the target network update interval "
+                          f"({self.n_envs} > {self.target_update_interval}), therefore the target network will be updated "
+                          "after each call to env.step() which corresponds to "
+                          f"{self.n_envs} steps.")
+
+    # ---- SB3 BaseAlgorithm surface ----------------------------------------------------------------------------------
+    @property
+    def logger(self):
+        return self._logger
+
+    def set_logger(self, logger) -> None:
+        self._logger = logger
+        self._custom_logger = True
+
+    def get_env(self):
+        return self.env
+
+    def _init_callback(self, callback):
+        if callback is None:
+            callback = _NullCallback()
+        elif isinstance(callback, (list, tuple)):
+            callback = _CallbackList(callback)
+        callback.init_callback(self)
+        return callback
+
+    def _setup_learn(self, total_timesteps: int, callback, reset_num_timesteps: bool):
+        self.start_time = time.time_ns()
+        if self.ep_info_buffer is None or reset_num_timesteps:
+            self.ep_info_buffer = collections.deque(maxlen=self._stats_window_size)
+        if reset_num_timesteps:
+            self.num_timesteps = 0
+            self._episode_num = 0
+        else:
+            total_timesteps += self.num_timesteps
+        self._total_timesteps = total_timesteps
+        self._num_timesteps_at_start = self.num_timesteps
+        if reset_num_timesteps or self._last_obs is None:
+            self._last_obs = self.env.reset()
+            self._last_episode_starts = np.ones((self.env.num_envs,), dtype=bool)
+        if not self._custom_logger and self._logger is None:
+            self._logger = imit_logger.Logger(None, [])
+        return total_timesteps, self._init_callback(callback)
+
+    def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
+        """[SB3 DQN.predict]: ONE `np.random.rand()` per call decides for the whole batch."""
+        if not deterministic and np.random.rand() < self.exploration_rate:
+            self.last_action_branch = "explore"
+            observation = np.asarray(observation)
+            if observation.shape != tuple(self.observation_space.shape):
+                action = np.array([self.action_space.sample() for _ in range(observation.shape[0])])
+            else:
+                action = np.array(self.action_space.sample())
+            return action, state
+        self.last_action_branch = "greedy"
+        return self.policy.predict(observation, state, episode_start, deterministic)
+
+    def _sample_action(self, learning_starts: int, n_envs: int) -> np.ndarray:
+        if self.num_timesteps < learning_starts:
+            self.last_action_branch = "warmup"
+            return np.array([self.action_space.sample() for _ in range(n_envs)])
+        action, _ = self.predict(self._last_obs, deterministic=False)
+        return action
+
+    def _store_transition(self, buffer_action, new_obs, reward, dones, infos) -> None:
+        next_obs = copy.deepcopy(new_obs)
+        for i, done in enumerate(dones):
+            if done and infos[i].get("terminal_observation") is not None:
+                next_obs[i] = infos[i]["terminal_observation"]
+        self.replay_buffer.add(self._last_obs, next_obs, buffer_action, reward, dones, infos)
+        self._last_obs = new_obs
+
+    def _on_step(self) -> None:
+        self._n_calls += 1
+        if self._n_calls % max(self.target_update_interval // self.n_envs, 1) == 0:
+            self.policy.polyak_update(self.tau)
+        self.exploration_rate = self.exploration_schedule(self._current_progress_remaining)
+        self.logger.record("rollout/exploration_rate", self.exploration_rate)
+
+    def _dump_logs(self) -> None:
+        elapsed = max((time.time_ns() - self.start_time) / 1e9, sys.float_info.epsilon)
+        fps = int((self.num_timesteps - self._num_timesteps_at_start) / elapsed)
+        self.logger.record("time/episodes", self._episode_num, exclude="tensorboard")
+        if len(self.ep_info_buffer) > 0 and len(self.ep_info_buffer[0]) > 0:
+            self.logger.record("rollout/ep_rew_mean", float(np.mean([e["r"] for e in self.ep_info_buffer])))
+            self.logger.record("rollout/ep_len_mean", float(np.mean([e["l"] for e in self.ep_info_buffer])))
+        self.logger.record("time/fps", fps)
+        self.logger.record("time/time_elapsed", int(elapsed), exclude="tensorboard")
+        self.logger.record("time/total_timesteps", self.num_timesteps, exclude="tensorboard")
+        self.logger.dump(step=self.num_timesteps)
+
+    def collect_rollouts(self, env, callback, train_freq: int, learning_starts: int, log_interval) -> Tuple[int, bool]:
+        """[SB3 OffPolicyAlgorithm.collect_rollouts] -> (timesteps collected, continue training)."""
+        self.policy.set_training_mode(False)
+        steps = 0
+        callback.on_rollout_start()
+        while steps < train_freq:
+            actions = self._sample_action(learning_starts, env.num_envs)
+            new_obs, rewards, dones, infos = env.step(actions)
+            self.num_timesteps += env.num_envs
+            steps += 1
+            callback.update_locals(locals())
+            if not callback.on_step():
+                return steps * env.num_envs, False
+            for info in infos:
+                if info.get("episode") is not None:
+                    self.ep_info_buffer.extend([info["episode"]])
+            self._store_transition(actions, new_obs, rewards, dones, infos)
+            self._current_progress_remaining = 1.0 - float(self.num_timesteps) / float(self._total_timesteps)
+            self._on_step()
+            for done in dones:
+                if done:
+                    self._episode_num += 1
+                    if log_interval is not None and self._episode_num % log_interval == 0:
+                        self._dump_logs()
+        callback.on_rollout_end()
+        return steps * env.num_envs, True
+
+    def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "DQN",
+              reset_num_timesteps: bool = True, progress_bar: bool = False):
+        if progress_bar:
+            raise NotImplementedError("the progress bar is not implemented")
+        require_device(self.device)
+        total_timesteps, callback = self._setup_learn(total_timesteps, callback, reset_num_timesteps)
+        callback.on_training_start(locals(), globals())
+        while self.num_timesteps < total_timesteps:
+            collected, go_on = self.collect_rollouts(self.env, callback, self.train_freq, self.learning_starts, log_interval)
+            if not go_on:
+                break
+            if self.num_timesteps > 0 and self.num_timesteps > self.learning_starts:
+                gradient_steps = self.gradient_steps if self.gradient_steps >= 0 else collected
+                if gradient_steps > 0:
+                    self.train(batch_size=self.batch_size, gradient_steps=gradient_steps)
+        callback.on_training_end()
+        return self
+
+    def train(self, gradient_steps: int, batch_size: int = 100) -> None:
+        """[SB3 DQN.train]: the index draws of all `gradient_steps` minibatches first (the same global-stream draws in
+        the same order: nothing else draws in between), one upload, the update, one read-back."""
+        self.policy.set_training_mode(True)
+        lr = self.lr_schedule(self._current_progress_remaining)
+        self.logger.record("train/learning_rate", lr)
+        rows = np.empty((gradient_steps, batch_size), np.int64)
+        n_new = batch_size
+        for s in range(gradient_steps):
+            rows[s], n_new = self.replay_buffer.sample_rows(batch_size)
+        self.last_sample_rows, self.last_n_new = rows, n_new
+        idx_dev = th.from_numpy(rows).to(self.device)
+        stats = th.empty(gradient_steps, 2, device=self.device)
+        self.policy.update(self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev, n_new, gradient_steps,
+                           batch_size, self.gamma, self.max_grad_norm, lr, stats)
+        self.last_train_stats = stats.cpu().numpy()
+        self._n_updates += gradient_steps
+        self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
+        self.logger.record("train/loss", np.mean(self.last_train_stats[:, 0].astype(np.float64)))

@@ -872,6 +872,41 @@ int ia_mce_forward(const double* T, const double* pi, const double* init, int S,
 int ia_mce_weights(const double* Dcum, const double* demo_om, int S, float* w, double* stats, void* stream);
 int ia_mce_norms(const float* grads, const float* params, int64_t n, double* stats, void* stream);
 
+/* ---- DQN / SQIL (dqn.hip; algorithms/sqil.py over [SB3 dqn.py]) ----
+ * The Q-network is a D -> H -> H -> A ReLU stack, flat parameters in torch order W1[H,D], b1, W2[H,H], b2, W3[A,H], b3.
+ * ia_dqn_update: n_steps consecutive gradient steps of DQN.train in one launch of ONE workgroup (launches of at most 32
+ * steps). Step s takes rows idx[s*B .. s*B + B): the first n_new index the learner ring, the rest the expert table
+ * (obs / next_obs [N, D], action int64 [N], reward, done float [N]); a table no row comes from may be NULL. Per step:
+ *   target = r + (1 - done) * gamma * max_a' Q_target(s', a'); loss = mean smooth_l1(Q(s, a), target) (beta = 1);
+ *   clip_grad_norm_(max_grad_norm); torch's Adam with adam_scalars[2s] = lr / (1 - b1^t), adam_scalars[2s + 1] =
+ *   sqrt(1 - b2^t) (a HOST array of 2 * n_steps floats formed by the caller in double, as ia_adam_step takes them).
+ * params / exp_avg / exp_avg_sq are updated in place, target_params is read; stats[2s] = loss, stats[2s + 1] = gradient
+ * norm before clipping; grad_out (nullable, param_count floats) = the last step's clipped gradient. Every sum has a
+ * fixed order: a launch repeats bit for bit and n launches of one step equal one launch of n.
+ * Covered (ia_dqn_update_ok): H in {32, 64}, D <= 64, A <= 16, B <= 256; IA_ERR_UNSUPPORTED otherwise. */
+int ia_dqn_update_ok(int D, int H, int A, int B);
+int ia_dqn_update(int D, int H, int A, int B, int n_new, int n_steps, float* params, const float* target_params,
+                  float* exp_avg, float* exp_avg_sq, const float* ring_obs, const float* ring_next_obs,
+                  const int64_t* ring_act, const float* ring_rew, const float* ring_done, const float* exp_obs,
+                  const float* exp_next_obs, const int64_t* exp_act, const float* exp_rew, const float* exp_done,
+                  const int64_t* idx, float gamma, float max_grad_norm, double beta1, double beta2, float eps,
+                  const float* adam_scalars, float* stats, float* grad_out, void* stream);
+/* q[n, A] and argmax[n] (first maximum) of that Q-network on obs[n, D]; 64 rows per workgroup, a row's result does not
+ * depend on the other rows or on n. Same D / H / A limits. */
+int ia_dqn_q_values(int D, int H, int A, const float* params, const float* obs, int n, float* q, int64_t* argmax,
+                    void* stream);
+/* The TD loss of any Q-network: from q[B, A] = Q(s, .), q_target[B, A] = Q_target(s', .): dq[B, A] = d loss / d q (non-zero
+ * in the taken action's column only), terms[B] = the per-row Huber terms, loss[0] = their mean (fixed order). */
+int ia_dqn_td_loss(const float* q, const float* q_target, const int64_t* actions, const float* rewards, const float* dones,
+                   int B, int A, float gamma, float* dq, float* terms, float* loss, void* stream);
+/* torch.optim.Adam's step over a flat buffer as ia_adam_step, but with the betas in double: `1 - beta` is formed in double
+ * and then rounded, as torch does (ia_adam_step forms it in float32: 1.f - 0.999f is off by 1.3e-5 relative, which the
+ * SQIL fixtures' tolerance does not absorb). The fused update uses the same element function. */
+int ia_dqn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double beta1,
+                     double beta2, float eps, float weight_decay, float step_size, float bc2_sqrt, void* stream);
+/* [SB3 utils.polyak_update] target = tau * online + (1 - tau) * target over n floats (tau == 1: a copy). */
+int ia_polyak_update(const float* online, float* target, int64_t n, float tau, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
