@@ -99,20 +99,25 @@ class ReplayIndex:
 
 
 class _Table:
-    """Flat device table of transitions: obs / next_obs [N, D] float32, action int64 [N], reward, done float32 [N]."""
+    """Flat device table of transitions: obs / next_obs [N, D] float32, action int64 [N] (Discrete) or float32 [N, A]
+    (Box, `act_dim` = A), reward, done float32 [N]."""
 
-    def __init__(self, rows: int, obs_dim: int, device):
-        self.rows, self.obs_dim = int(rows), int(obs_dim)
+    def __init__(self, rows: int, obs_dim: int, device, act_dim: Optional[int] = None):
+        self.rows, self.obs_dim, self.act_dim = int(rows), int(obs_dim), act_dim
         self.obs = th.zeros(self.rows, obs_dim, device=device)
         self.next_obs = th.zeros(self.rows, obs_dim, device=device)
-        self.action = th.zeros(self.rows, dtype=th.int64, device=device)
+        if act_dim is None:
+            self.action = th.zeros(self.rows, dtype=th.int64, device=device)
+        else:
+            self.action = th.zeros(self.rows, int(act_dim), device=device)
         self.reward = th.zeros(self.rows, device=device)
         self.done = th.zeros(self.rows, device=device)
 
     def write(self, lo: int, obs, next_obs, action, reward, done) -> None:
         n = len(obs)
+        act = (np.int64, (n,)) if self.act_dim is None else (np.float32, (n, self.act_dim))
         for dst, src, dtype, shape in ((self.obs, obs, np.float32, (n, -1)), (self.next_obs, next_obs, np.float32, (n, -1)),
-                                       (self.action, action, np.int64, (n,)), (self.reward, reward, np.float32, (n,)),
+                                       (self.action, action) + act, (self.reward, reward, np.float32, (n,)),
                                        (self.done, done, np.float32, (n,))):
             dst[lo:lo + n].copy_(th.from_numpy(np.array(src, dtype).reshape(shape)))
 
@@ -122,7 +127,7 @@ def _device(device) -> th.device:
 
 
 class ReplayBuffer:
-    """[SB3 buffers.ReplayBuffer] for flat Box observations and Discrete actions, its rows in device memory.
+    """[SB3 buffers.ReplayBuffer] for flat Box observations and Discrete or flat Box actions, its rows in device memory.
     `handle_timeout_termination`: a `done` that is a time-limit truncation does not cut the bootstrap (the product
     `done * (1 - timeout)` SB3 forms when sampling is formed when the row is stored)."""
 
@@ -130,16 +135,18 @@ class ReplayBuffer:
                  optimize_memory_usage: bool = False, handle_timeout_termination: bool = True):
         if optimize_memory_usage:
             raise NotImplementedError("optimize_memory_usage is not implemented")
-        if not isinstance(observation_space, spaces.Box) or not isinstance(action_space, spaces.Discrete):
-            raise NotImplementedError("the replay buffer holds flat Box observations and Discrete actions")
+        if not isinstance(observation_space, spaces.Box) or not isinstance(action_space, (spaces.Discrete, spaces.Box)):
+            raise NotImplementedError("the replay buffer holds flat Box observations and Discrete or Box actions")
         self.observation_space, self.action_space = observation_space, action_space
         self.obs_dim = int(np.prod(observation_space.shape))
+        # Box actions: a float32 [rows, A] column; Discrete: the int64 [rows] column
+        self.act_dim = int(np.prod(action_space.shape)) if isinstance(action_space, spaces.Box) else None
         self.device = _device(device)
         self.n_envs = int(n_envs)
         self.index = ReplayIndex(buffer_size, n_envs)
         self.buffer_size = self.index.buffer_size
         self.handle_timeout_termination = handle_timeout_termination
-        self.table = _Table(self.buffer_size * self.n_envs, self.obs_dim, self.device)
+        self.table = _Table(self.buffer_size * self.n_envs, self.obs_dim, self.device, self.act_dim)
 
     @property
     def pos(self) -> int:
@@ -170,7 +177,7 @@ class ReplayBuffer:
 
     def _gather(self, table: _Table, rows: np.ndarray) -> ReplayBufferSamples:
         idx = th.from_numpy(rows).to(self.device)
-        return ReplayBufferSamples(table.obs[idx], table.action[idx].reshape(-1, 1), table.next_obs[idx],
+        return ReplayBufferSamples(table.obs[idx], table.action[idx].reshape(-1, table.act_dim or 1), table.next_obs[idx],
                                    table.done[idx].reshape(-1, 1), table.reward[idx].reshape(-1, 1))
 
     def sample(self, batch_size: int, env=None) -> ReplayBufferSamples:
@@ -449,7 +456,129 @@ MlpPolicy = DQNPolicy
 
 
 class OffPolicyAlgorithm:
-    """Marker base, as `ppo.OnPolicyAlgorithm`."""
+    """What [SB3 common/off_policy_algorithm.py] gives DQN and TD3 alike: the `BaseAlgorithm` surface, `learn`,
+    `collect_rollouts`, `_store_transition` and `_dump_logs`. A subclass supplies `_sample_action`, `_on_step`, `train`."""
+
+    # ---- SB3 BaseAlgorithm surface ----------------------------------------------------------------------------------
+    @property
+    def logger(self):
+        return self._logger
+
+    def set_logger(self, logger) -> None:
+        self._logger = logger
+        self._custom_logger = True
+
+    def get_env(self):
+        return self.env
+
+    def _init_callback(self, callback):
+        if callback is None:
+            callback = _NullCallback()
+        elif isinstance(callback, (list, tuple)):
+            callback = _CallbackList(callback)
+        callback.init_callback(self)
+        return callback
+
+    def _setup_learn(self, total_timesteps: int, callback, reset_num_timesteps: bool):
+        self.start_time = time.time_ns()
+        if self.ep_info_buffer is None or reset_num_timesteps:
+            self.ep_info_buffer = collections.deque(maxlen=self._stats_window_size)
+        if reset_num_timesteps:
+            self.num_timesteps = 0
+            self._episode_num = 0
+        else:
+            total_timesteps += self.num_timesteps
+        self._total_timesteps = total_timesteps
+        self._num_timesteps_at_start = self.num_timesteps
+        if reset_num_timesteps or self._last_obs is None:
+            self._last_obs = self.env.reset()
+            self._last_episode_starts = np.ones((self.env.num_envs,), dtype=bool)
+        if not self._custom_logger and self._logger is None:
+            self._logger = imit_logger.Logger(None, [])
+        return total_timesteps, self._init_callback(callback)
+
+    def _store_transition(self, buffer_action, new_obs, reward, dones, infos) -> None:
+        next_obs = copy.deepcopy(new_obs)
+        for i, done in enumerate(dones):
+            if done and infos[i].get("terminal_observation") is not None:
+                next_obs[i] = infos[i]["terminal_observation"]
+        self.replay_buffer.add(self._last_obs, next_obs, buffer_action, reward, dones, infos)
+        self._last_obs = new_obs
+
+    def _on_step(self) -> None:
+        pass
+
+    def _on_episode_end(self, env_index: int, n_envs: int) -> None:
+        """[SB3 collect_rollouts]: where an episode's end resets the action noise."""
+
+    def _dump_logs(self) -> None:
+        elapsed = max((time.time_ns() - self.start_time) / 1e9, sys.float_info.epsilon)
+        fps = int((self.num_timesteps - self._num_timesteps_at_start) / elapsed)
+        self.logger.record("time/episodes", self._episode_num, exclude="tensorboard")
+        if len(self.ep_info_buffer) > 0 and len(self.ep_info_buffer[0]) > 0:
+            self.logger.record("rollout/ep_rew_mean", float(np.mean([e["r"] for e in self.ep_info_buffer])))
+            self.logger.record("rollout/ep_len_mean", float(np.mean([e["l"] for e in self.ep_info_buffer])))
+        self.logger.record("time/fps", fps)
+        self.logger.record("time/time_elapsed", int(elapsed), exclude="tensorboard")
+        self.logger.record("time/total_timesteps", self.num_timesteps, exclude="tensorboard")
+        self.logger.dump(step=self.num_timesteps)
+
+    def collect_rollouts(self, env, callback, train_freq, learning_starts: int, log_interval) -> Tuple[int, bool]:
+        """[SB3 OffPolicyAlgorithm.collect_rollouts] -> (timesteps collected, continue training). `train_freq`: a number of
+        steps, or SB3's pair (n, "step" | "episode"); episodes need one environment, as there."""
+        self.policy.set_training_mode(False)
+        steps, episodes = 0, 0
+        freq, unit = train_freq if isinstance(train_freq, tuple) else (train_freq, "step")
+        assert freq > 0, "Should at least collect one step or episode."
+        if env.num_envs > 1:
+            assert unit == "step", "You must use only one env when doing episodic training."
+        callback.on_rollout_start()
+        # [SB3 utils.should_collect_more_steps]
+        while (steps < freq) if unit == "step" else (episodes < freq):
+            actions = self._sample_action(learning_starts, env.num_envs)
+            # (a learner with continuous actions returns the pair (env action, buffer action))
+            actions, buffer_actions = actions if isinstance(actions, tuple) else (actions, actions)
+            new_obs, rewards, dones, infos = env.step(actions)
+            self.num_timesteps += env.num_envs
+            steps += 1
+            callback.update_locals(locals())
+            if not callback.on_step():
+                return steps * env.num_envs, False
+            for info in infos:
+                if info.get("episode") is not None:
+                    self.ep_info_buffer.extend([info["episode"]])
+            self._store_transition(buffer_actions, new_obs, rewards, dones, infos)
+            self._current_progress_remaining = 1.0 - float(self.num_timesteps) / float(self._total_timesteps)
+            self._on_step()
+            for i, done in enumerate(dones):
+                if done:
+                    episodes += 1
+                    self._episode_num += 1
+                    self._on_episode_end(i, env.num_envs)
+                    if log_interval is not None and self._episode_num % log_interval == 0:
+                        self._dump_logs()
+        callback.on_rollout_end()
+        return steps * env.num_envs, True
+
+    def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "DQN",
+              reset_num_timesteps: bool = True, progress_bar: bool = False):
+        if progress_bar:
+            raise NotImplementedError("the progress bar is not implemented")
+        require_device(self.device)
+        total_timesteps, callback = self._setup_learn(total_timesteps, callback, reset_num_timesteps)
+        callback.on_training_start(locals(), globals())
+        while self.num_timesteps < total_timesteps:
+            collected, go_on = self.collect_rollouts(self.env, callback, self.train_freq, self.learning_starts, log_interval)
+            if not go_on:
+                break
+            if self.num_timesteps > 0 and self.num_timesteps > self.learning_starts:
+                gradient_steps = self.gradient_steps if self.gradient_steps >= 0 else collected
+                if gradient_steps > 0:
+                    self.train(batch_size=self.batch_size, gradient_steps=gradient_steps)
+        callback.on_training_end()
+        return self
+
+
 
 
 class DQN(OffPolicyAlgorithm):
@@ -536,44 +665,6 @@ class DQN(OffPolicyAlgorithm):
                           "after each call to env.step() which corresponds to "
                           f"{self.n_envs} steps.")
 
-    # ---- SB3 BaseAlgorithm surface ----------------------------------------------------------------------------------
-    @property
-    def logger(self):
-        return self._logger
-
-    def set_logger(self, logger) -> None:
-        self._logger = logger
-        self._custom_logger = True
-
-    def get_env(self):
-        return self.env
-
-    def _init_callback(self, callback):
-        if callback is None:
-            callback = _NullCallback()
-        elif isinstance(callback, (list, tuple)):
-            callback = _CallbackList(callback)
-        callback.init_callback(self)
-        return callback
-
-    def _setup_learn(self, total_timesteps: int, callback, reset_num_timesteps: bool):
-        self.start_time = time.time_ns()
-        if self.ep_info_buffer is None or reset_num_timesteps:
-            self.ep_info_buffer = collections.deque(maxlen=self._stats_window_size)
-        if reset_num_timesteps:
-            self.num_timesteps = 0
-            self._episode_num = 0
-        else:
-            total_timesteps += self.num_timesteps
-        self._total_timesteps = total_timesteps
-        self._num_timesteps_at_start = self.num_timesteps
-        if reset_num_timesteps or self._last_obs is None:
-            self._last_obs = self.env.reset()
-            self._last_episode_starts = np.ones((self.env.num_envs,), dtype=bool)
-        if not self._custom_logger and self._logger is None:
-            self._logger = imit_logger.Logger(None, [])
-        return total_timesteps, self._init_callback(callback)
-
     def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
         """[SB3 DQN.predict]: ONE `np.random.rand()` per call decides for the whole batch."""
         if not deterministic and np.random.rand() < self.exploration_rate:
@@ -594,77 +685,12 @@ class DQN(OffPolicyAlgorithm):
         action, _ = self.predict(self._last_obs, deterministic=False)
         return action
 
-    def _store_transition(self, buffer_action, new_obs, reward, dones, infos) -> None:
-        next_obs = copy.deepcopy(new_obs)
-        for i, done in enumerate(dones):
-            if done and infos[i].get("terminal_observation") is not None:
-                next_obs[i] = infos[i]["terminal_observation"]
-        self.replay_buffer.add(self._last_obs, next_obs, buffer_action, reward, dones, infos)
-        self._last_obs = new_obs
-
     def _on_step(self) -> None:
         self._n_calls += 1
         if self._n_calls % max(self.target_update_interval // self.n_envs, 1) == 0:
             self.policy.polyak_update(self.tau)
         self.exploration_rate = self.exploration_schedule(self._current_progress_remaining)
         self.logger.record("rollout/exploration_rate", self.exploration_rate)
-
-    def _dump_logs(self) -> None:
-        elapsed = max((time.time_ns() - self.start_time) / 1e9, sys.float_info.epsilon)
-        fps = int((self.num_timesteps - self._num_timesteps_at_start) / elapsed)
-        self.logger.record("time/episodes", self._episode_num, exclude="tensorboard")
-        if len(self.ep_info_buffer) > 0 and len(self.ep_info_buffer[0]) > 0:
-            self.logger.record("rollout/ep_rew_mean", float(np.mean([e["r"] for e in self.ep_info_buffer])))
-            self.logger.record("rollout/ep_len_mean", float(np.mean([e["l"] for e in self.ep_info_buffer])))
-        self.logger.record("time/fps", fps)
-        self.logger.record("time/time_elapsed", int(elapsed), exclude="tensorboard")
-        self.logger.record("time/total_timesteps", self.num_timesteps, exclude="tensorboard")
-        self.logger.dump(step=self.num_timesteps)
-
-    def collect_rollouts(self, env, callback, train_freq: int, learning_starts: int, log_interval) -> Tuple[int, bool]:
-        """[SB3 OffPolicyAlgorithm.collect_rollouts] -> (timesteps collected, continue training)."""
-        self.policy.set_training_mode(False)
-        steps = 0
-        callback.on_rollout_start()
-        while steps < train_freq:
-            actions = self._sample_action(learning_starts, env.num_envs)
-            new_obs, rewards, dones, infos = env.step(actions)
-            self.num_timesteps += env.num_envs
-            steps += 1
-            callback.update_locals(locals())
-            if not callback.on_step():
-                return steps * env.num_envs, False
-            for info in infos:
-                if info.get("episode") is not None:
-                    self.ep_info_buffer.extend([info["episode"]])
-            self._store_transition(actions, new_obs, rewards, dones, infos)
-            self._current_progress_remaining = 1.0 - float(self.num_timesteps) / float(self._total_timesteps)
-            self._on_step()
-            for done in dones:
-                if done:
-                    self._episode_num += 1
-                    if log_interval is not None and self._episode_num % log_interval == 0:
-                        self._dump_logs()
-        callback.on_rollout_end()
-        return steps * env.num_envs, True
-
-    def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "DQN",
-              reset_num_timesteps: bool = True, progress_bar: bool = False):
-        if progress_bar:
-            raise NotImplementedError("the progress bar is not implemented")
-        require_device(self.device)
-        total_timesteps, callback = self._setup_learn(total_timesteps, callback, reset_num_timesteps)
-        callback.on_training_start(locals(), globals())
-        while self.num_timesteps < total_timesteps:
-            collected, go_on = self.collect_rollouts(self.env, callback, self.train_freq, self.learning_starts, log_interval)
-            if not go_on:
-                break
-            if self.num_timesteps > 0 and self.num_timesteps > self.learning_starts:
-                gradient_steps = self.gradient_steps if self.gradient_steps >= 0 else collected
-                if gradient_steps > 0:
-                    self.train(batch_size=self.batch_size, gradient_steps=gradient_steps)
-        callback.on_training_end()
-        return self
 
     def train(self, gradient_steps: int, batch_size: int = 100) -> None:
         """[SB3 DQN.train]: the index draws of all `gradient_steps` minibatches first (the same global-stream draws in

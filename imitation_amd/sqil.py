@@ -1,8 +1,10 @@
 """Soft Q Imitation Learning (`algorithms/sqil.py`, https://arxiv.org/abs/1905.11108): DQN-style Q-learning on a replay
 buffer whose minibatches are half learner transitions with reward 0 and half expert demonstrations with reward 1.
 
-`SQIL` and `SQILReplayBuffer` keep the reference's surface; the learner is this package's `DQN` (`imitation_amd/dqn.py`),
-whose update runs on the device from the learner ring and the expert table by index.
+`SQIL` and `SQILReplayBuffer` keep the reference's surface; the learner is this package's `DQN` (`imitation_amd/dqn.py`)
+or, on Box actions, its `TD3` / `DDPG` (`imitation_amd/td3.py`), whose updates run on the device from the learner ring and
+the expert table by index. Demonstrated actions enter the expert table as given: the reference does not scale them to
+[-1, 1] either (`sqil.py:196-204`), while the learner ring holds scaled actions.
 """
 from __future__ import annotations
 
@@ -13,6 +15,7 @@ import numpy as np
 from imitation_amd import data_types as dt
 from imitation_amd import dqn
 from imitation_amd import logger as imit_logger
+from imitation_amd import td3
 from imitation_amd.vec_env import VecEnv
 
 
@@ -53,7 +56,7 @@ class SQILReplayBuffer(dqn.ReplayBuffer):
         # one `add` per demonstration into a ring of n positions with one env each: reward 1, the table is full afterwards
         self.expert_index = dqn.ReplayIndex(n, 1)
         self.expert_index.fill()
-        self.expert = dqn._Table(n, self.obs_dim, self.device)
+        self.expert = dqn._Table(n, self.obs_dim, self.device, self.act_dim)
         self.expert.write(0, demonstrations.obs, demonstrations.next_obs, demonstrations.acts, np.ones(n, np.float32),
                           demonstrations.dones)
 
@@ -92,9 +95,9 @@ class SQIL:
             raise ValueError("SQIL uses a custom replay buffer: 'replay_buffer_class' not allowed.")
         if "replay_buffer_kwargs" in rl_kwargs:
             raise ValueError("SQIL uses a custom replay buffer: 'replay_buffer_kwargs' not allowed.")
-        if not (isinstance(rl_algo_class, type) and issubclass(rl_algo_class, dqn.DQN)):
-            raise NotImplementedError(f"rl_algo_class {rl_algo_class}: only this package's DQN is implemented "
-                                      "(SAC / TD3 / DDPG learners are out of scope, DESIGN section 1)")
+        if not (isinstance(rl_algo_class, type) and issubclass(rl_algo_class, (dqn.DQN, td3.TD3))):
+            raise NotImplementedError(f"rl_algo_class {rl_algo_class}: only this package's DQN, TD3 and DDPG are implemented "
+                                      "(SAC is out of scope, DESIGN section 1)")
         self.rl_algo = rl_algo_class(policy=policy, env=venv, replay_buffer_class=SQILReplayBuffer,
                                      replay_buffer_kwargs={"demonstrations": demonstrations}, **rl_kwargs)
         # `algorithms/base.py:139-166` DemonstrationAlgorithm.__init__
@@ -119,6 +122,6 @@ class SQIL:
         self.rl_algo.learn(total_timesteps=total_timesteps, tb_log_name=tb_log_name, **kwargs)
 
     @property
-    def policy(self) -> dqn.DQNPolicy:
-        assert isinstance(self.rl_algo.policy, dqn.DQNPolicy)
+    def policy(self):
+        assert isinstance(self.rl_algo.policy, (dqn.DQNPolicy, td3.TD3Policy))
         return self.rl_algo.policy

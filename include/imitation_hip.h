@@ -907,6 +907,31 @@ int ia_dqn_adam_step(float* params, const float* grads, float* exp_avg, float* e
 /* [SB3 utils.polyak_update] target = tau * online + (1 - tau) * target over n floats (tau == 1: a copy). */
 int ia_polyak_update(const float* online, float* target, int64_t n, float tau, void* stream);
 
+/* ---- TD3 / DDPG ([SB3 td3/td3.py] TD3.train; csrc/td3.hip) -------------------------------------------------------
+ * The pieces of one gradient step around ia_mlp_forward / ia_mlp_backward (actor D -> ... -> A with a tanh output,
+ * critics D + A -> ... -> 1, their targets), each ONE launch; all sums in a fixed order, no float atomics.
+ * ia_td3_assemble: the minibatch of index row idx[B] (rows < n_new index the learner ring, the rest the expert table;
+ * either count may be 0 and its table NULL): X[B, ld] = [obs | action | 0 ...] (ld >= D + A), S[B, D] = obs,
+ * S2[B, D] = next_obs, rew[B], done[B]. Actions are float32 [rows, A]. An index outside [0, rows) yields NaN. */
+int ia_td3_assemble(const float* ring_obs, const float* ring_next_obs, const float* ring_act, const float* ring_rew,
+                    const float* ring_done, int64_t ring_rows, const float* exp_obs, const float* exp_next_obs,
+                    const float* exp_act, const float* exp_rew, const float* exp_done, int64_t exp_rows, const int64_t* idx,
+                    int B, int n_new, int D, int A, int ld, float* X, float* S, float* S2, float* rew, float* done,
+                    void* stream);
+/* X2[B, ld] = [S2 | clamp(mu_target + clamp(noise, -noise_clip, noise_clip), -1, 1) | 0 ...]; mu_target, noise [B, A]. */
+int ia_td3_target_input(const float* S2, const float* mu_target, const float* noise, int B, int D, int A, int ld,
+                        float noise_clip, float* X2, void* stream);
+/* q, q_target, dq: [n_critics][B], n_critics 1 or 2. y[b] = rew + (1 - done) * gamma * min_i q_target[i][b] (y nullable),
+ * loss[0] = sum_i mean_b (q[i][b] - y[b])^2, dq[i][b] = 2 (q[i][b] - y[b]) / B. */
+int ia_td3_critic_loss(const float* q, const float* q_target, const float* rewards, const float* dones, int B, int n_critics,
+                       float gamma, float* dq, float* y, float* loss, void* stream);
+/* X[b, D + a] = mu[b, a]: the actor's output as the action columns of the first critic's input. */
+int ia_td3_actor_input(const float* mu, int B, int D, int A, int ld, float* X, void* stream);
+/* loss[0] = -mean(q1); dmu[b, a] = dX[b, D + a] * (-1 / B) * (1 - mu[b, a]^2), with dX[B, ld] = d sum(q1) / dX from
+ * ia_mlp_backward (dOut = 1), which does not apply the output tanh's derivative. */
+int ia_td3_actor_seed(const float* q1, const float* dX, const float* mu, int B, int D, int A, int ld, float* dmu, float* loss,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
