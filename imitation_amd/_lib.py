@@ -95,6 +95,18 @@ class DiscStepArgs(C.Structure):
                  ("gp_out", C.c_void_p)])
 
 
+class OffpolicyStepArgs(C.Structure):
+    """Mirror of `ia_offpolicy_step_args` (include/imitation_hip.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("obs", "next_obs", "act_i64", "act_f32", "ring_act_f32", "dones", "ring_done")] +
+                [(n, C.c_int) for n in ("n", "obs_dim", "act_dim", "use_state", "use_action", "use_next_state", "use_done")] +
+                [("desc", C.POINTER(MlpDesc))] + [(n, C.c_void_p) for n in ("params", "norm_mean", "norm_var")] +
+                [("norm_eps", C.c_float), ("out_act", C.c_int), ("rewards_in", C.c_void_p)] +
+                [(n, C.c_void_p) for n in ("ring_obs", "ring_next_obs", "ring_action_i64", "ring_action_f32", "ring_reward",
+                                           "ring_done_out")] + [("ring_row", C.c_int64), ("ring_rows", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("tile_obs", "tile_next_obs", "tile_act_i64", "tile_act_f32", "tile_dones")] +
+                [("tile_row", C.c_int64), ("tile_rows", C.c_int64), ("rewards_host", C.c_void_p)])
+
+
 class HipExtensionMissing(RuntimeError):
     pass
 
@@ -269,6 +281,9 @@ _SIGS = {
     "ia_td3_critic_loss": ([_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P], C.c_int),
     "ia_td3_actor_input": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
     "ia_td3_actor_seed": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P], C.c_int),
+    "ia_offpolicy_step_rows": ([], C.c_int),
+    "ia_offpolicy_step_ok": ([C.POINTER(MlpDesc), _I, _I, _I, _I, _I, _I], C.c_int),
+    "ia_offpolicy_step": ([C.POINTER(OffpolicyStepArgs), _P], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

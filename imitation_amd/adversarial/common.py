@@ -24,6 +24,7 @@ from torch import nn
 
 from imitation_amd import _lib as L
 from imitation_amd import buffer, data_types as dt
+from imitation_amd import dqn
 from imitation_amd import logger as imit_logger
 from imitation_amd import networks, ppo, reward_nets, wrappers
 from imitation_amd.networks import HipAdam, TransitionTable, require_device
@@ -189,6 +190,15 @@ class AdversarialTrainer(abc.ABC):
         if gen_replay_buffer_capacity is None:
             gen_replay_buffer_capacity = self.gen_train_timesteps
         self._gen_replay_buffer = buffer.ReplayBuffer(gen_replay_buffer_capacity, self.venv, device=self._device)
+        # off-policy generators (DQN, TD3, DDPG) under a state-holder reward net: one `ia_offpolicy_step` launch per
+        # environment step relabels the step and stores it to the learner's ring and to a per-round device tile
+        # (`dqn.RewardStepSource`); every other combination keeps the per-step host path of the wrapper
+        self._step_source = None
+        if self._offpolicy_fused_ok():
+            self._step_source = dqn.RewardStepSource(self.gen_algo.replay_buffer, self.reward_train,
+                                                       tile_steps=self._round_steps_bound())
+            self.gen_algo.replay_buffer.reward_source = self._step_source
+            self.venv_wrapped.step_source = self._step_source
 
         # ---- data parallelism over env batches (extension; the reference is single-process) ----
         self._dp = data_parallel
@@ -1037,6 +1047,25 @@ class AdversarialTrainer(abc.ABC):
             mlp.add_flat_grad(g)
         self.last_grad_penalty = pen
 
+    def _round_steps_bound(self) -> int:
+        """Environment steps of one `train_gen` at most: `learn` collects whole `train_freq` blocks until the round's
+        timesteps are reached (an episodic `train_freq` has no bound: the tile then grows on demand)."""
+        n = self.venv.num_envs
+        freq = getattr(self.gen_algo, "train_freq", 1)
+        freq = freq[0] if isinstance(freq, tuple) and freq[1] == "step" else (freq if isinstance(freq, int) else 1)
+        return -(-self.gen_train_timesteps // n) + int(freq)
+
+    def _offpolicy_fused_ok(self) -> bool:
+        """The learner's ring is exactly `dqn.ReplayBuffer`, the reward is a state-holder net whose per-step prediction is
+        the plain `predict_processed` (a wrapper with per-step state of its own, `NormalizedRewardNet`, is not), and
+        `IA_OFFPOLICY_FUSED` is not 0."""
+        ring = getattr(self.gen_algo, "replay_buffer", None)
+        net = None if self.debug_use_ground_truth else self.reward_train
+        return (isinstance(self.gen_algo, dqn.OffPolicyAlgorithm) and type(ring) is dqn.ReplayBuffer
+                and net is not None and not isinstance(net, nn.Module)
+                and type(net).predict_processed is reward_nets.RewardNet.predict_processed
+                and os.environ.get("IA_OFFPOLICY_FUSED", "1") != "0")
+
     # ---- generator update (`common.py:391-425`) -------------------------------------------------
     def train_gen(self, total_timesteps: Optional[int] = None, learn_kwargs: Optional[Mapping] = None) -> None:
         if total_timesteps is None:
@@ -1054,6 +1083,18 @@ class AdversarialTrainer(abc.ABC):
 
     def _store_gen_rollout(self) -> None:
         """The tail of `train_gen` (`common.py:407-420`): the rollout's transitions go to the replay buffer."""
+        src = self._step_source
+        if src is not None:
+            # the round's rows are in the device tile the step launches filled: only the row order crosses PCIe
+            n_rows = self.venv_buffering.n_transitions
+            order, ep_lens, T = self.venv_buffering.pop_order_and_lens()
+            self._check_fixed_horizon(ep_lens)
+            if order is not None:
+                if n_rows != src.tile_step * src.n:
+                    raise RuntimeError(f"the round tile holds {src.tile_step * src.n} rows, the buffering wrapper {n_rows}")
+                self._gen_replay_buffer.store_from_rollout(src.rollout_view(), order, infos=self.venv_buffering.last_infos)
+            self.venv_wrapped.end_round()
+            return
         rb = getattr(self.gen_algo, "rollout_buffer", None)
         device_rows = (isinstance(self.gen_algo, ppo.PPO) and rb is not None and rb.full
                        and self.venv_buffering.n_transitions == rb.buffer_size * rb.n_envs)

@@ -158,6 +158,10 @@ def load_reward_net(path, net) -> None:
 def save(trainer, save_path) -> None:
     """`scripts/train_adversarial.py:25-35`: discriminator and generator artefacts."""
     save_path = str(save_path)
+    from imitation_amd.dqn import OffPolicyAlgorithm
+    if isinstance(trainer.gen_algo, OffPolicyAlgorithm):
+        raise NotImplementedError(f"checkpoint.save with an off-policy generator ({type(trainer.gen_algo).__name__}) is "
+                                  "not implemented: the SB3 zip layout is written for PPO only")
     os.makedirs(save_path, exist_ok=True)
     save_reward_net(os.path.join(save_path, "reward_train.pt"), trainer.reward_train)
     save_reward_net(os.path.join(save_path, "reward_test.pt"), trainer.reward_test)

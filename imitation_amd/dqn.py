@@ -147,6 +147,8 @@ class ReplayBuffer:
         self.buffer_size = self.index.buffer_size
         self.handle_timeout_termination = handle_timeout_termination
         self.table = _Table(self.buffer_size * self.n_envs, self.obs_dim, self.device, self.act_dim)
+        # `RewardStepSource`: `add` then ignores its `reward` and stores the step with one `ia_offpolicy_step` launch
+        self.reward_source: Optional["RewardStepSource"] = None
 
     @property
     def pos(self) -> int:
@@ -164,6 +166,10 @@ class ReplayBuffer:
         if self.handle_timeout_termination:
             timeouts = np.array([info.get("TimeLimit.truncated", False) for info in infos], np.float32)
             done = done * (1 - timeouts)
+        if self.reward_source is not None:
+            self.reward_source.require_staged()   # (before the ring position moves)
+            self.reward_source.store_step(self.index.add() * self.n_envs, obs, next_obs, action, done)
+            return
         reward = np.array(np.broadcast_to(np.asarray(reward, np.float32), (self.n_envs,)))
         at = self.index.add()
         self.table.write(at * self.n_envs, obs, next_obs, action, reward, done)
@@ -186,6 +192,188 @@ class ReplayBuffer:
             raise NotImplementedError("VecNormalize is not implemented")
         rows, _ = ReplayBuffer.sample_rows(self, batch_size)
         return self._gather(self.table, rows)
+
+
+class RewardStepSource:
+    """The reward source of a learner ring under a learned reward (`AdversarialTrainer` installs it on
+    `ReplayBuffer.reward_source`): one `ia_offpolicy_step` launch per environment step (csrc/offpolicy.hip) relabels the
+    step's rows and writes them to the ring, to a per-round device tile (what the trainer's own replay ring is filled
+    from) and to a pinned host tile of rewards (the wrapper's episode bookkeeping), instead of a reward prediction with
+    its read-back followed by five small copies.
+
+    The step's rows go in through a ring of `SLOTS` pinned host records; a record is rewritten only after the launch that
+    read it has completed (one event per record, waited on only when the ring of records wraps). `RewardVecEnvWrapper`
+    stages the action the environment saw and the raw dones (`stage`); `ReplayBuffer.add` passes the learner's view of the
+    step (`store_step`). With a net whose `forward_plan` the kernel covers the reward is computed in the launch; any other
+    net's `predict_th` stays on the device and the launch reads it from there."""
+
+    SLOTS = 8
+
+    def __init__(self, ring: "ReplayBuffer", reward_net, slots: Optional[int] = None, tile_steps: int = 64):
+        self.ring, self.net = ring, reward_net
+        self.device = ring.device
+        self.n, self.od = ring.n_envs, ring.obs_dim
+        self.discrete = ring.act_dim is None
+        self.A = 1 if self.discrete else ring.act_dim
+        lib = L.load()
+        plan = reward_net.forward_plan()
+        self.base, self.out_act = None, L.ACT_NONE
+        if plan is not None:
+            base, out_act = plan
+            if lib.ia_offpolicy_step_ok(C.byref(base.mlp.desc), base.obs_dim, base.act_dim, *[int(f) for f in base.flags]):
+                self.base, self.out_act = base, out_act
+        self.act_dim = self.base.act_dim if self.base is not None else self.A
+        n, od, A = self.n, self.od, self.A
+        pin = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype).pin_memory()
+        self.slots = []
+        for _ in range(int(slots or self.SLOTS)):
+            rec = dict(obs=pin(n, od), next_obs=pin(n, od), dones=pin(n, dtype=th.uint8), ring_done=pin(n),
+                       act=pin(n, dtype=th.int64) if self.discrete else pin(n, A),
+                       ring_act=None if self.discrete else pin(n, A))
+            rec["np"] = {k: v.numpy() for k, v in rec.items() if v is not None}
+            self.slots.append(rec)
+        self.events: List[Optional[th.cuda.Event]] = [None] * len(self.slots)
+        self.launches = 0          # `ia_offpolicy_step` calls so far (tests count them)
+        self._slot_checked = -1
+        self._staged = -1          # the `launches` count at the latest `stage`
+        self.event_waits = 0       # records found still in flight when the ring of records wrapped
+        self.tile_step = 0         # steps in the round tile
+        self._alloc_tile(int(tile_steps))
+        self._args: List[Any] = [None] * len(self.slots)   # per record: (key, `OffpolicyStepArgs` with its pointers filled in)
+
+    def _alloc_tile(self, steps: int) -> None:
+        n, od, dev = self.n, self.od, self.device
+        old = getattr(self, "tile_obs", None)
+        olds = (self.tile_obs, self.tile_next, self.tile_act, self.tile_dones, self.rewards_host) if old is not None else None
+        self.tile_cap = steps
+        self.tile_obs = th.zeros((steps + 1) * n, od, device=dev)   # (one spare row block: `store_from_rollout`'s view)
+        self.tile_next = th.zeros(steps * n, od, device=dev)
+        self.tile_act = (th.zeros(steps * n, dtype=th.int64, device=dev) if self.discrete
+                         else th.zeros(steps * n, self.A, device=dev))
+        self.tile_dones = th.zeros(steps * n, dtype=th.uint8, device=dev)
+        self.rewards_host = th.zeros(steps, n).pin_memory()
+        self.rewards_np = self.rewards_host.numpy()
+        if olds is not None:   # a longer round than any before: the written rows move over (rare; one synchronisation)
+            th.cuda.current_stream().synchronize()
+            for new, o in zip((self.tile_obs, self.tile_next, self.tile_act, self.tile_dones, self.rewards_host), olds):
+                m = min(len(o), len(new))
+                new[:m].copy_(o[:m])
+            th.cuda.current_stream().synchronize()
+
+    def reward_row(self) -> np.ndarray:
+        """The row of the pinned reward tile the NEXT stored step fills (valid once that launch has completed)."""
+        if self.tile_step == self.tile_cap:
+            self._alloc_tile(2 * self.tile_cap)
+        return self.rewards_np[self.tile_step]
+
+    def _slot(self):
+        k = self.launches % len(self.slots)
+        if self._slot_checked != self.launches:   # (once per step: `stage` and `store_step` fill the same record)
+            self._slot_checked = self.launches
+            ev = self.events[k]
+            if ev is not None and not ev.query():
+                self.event_waits += 1
+                ev.synchronize()
+        return k, self.slots[k]["np"]
+
+    def stage(self, actions, dones) -> None:
+        """The action the environment executed (what the discriminator sees) and the raw dones of the step."""
+        _, rec = self._slot()
+        rec["act"][...] = np.asarray(actions).reshape(rec["act"].shape)
+        rec["dones"][...] = np.asarray(dones).reshape(-1)
+        self._staged = self.launches
+
+    def require_staged(self) -> None:
+        """A step can be stored only behind its `stage`: the record's discriminator action and raw dones would otherwise be
+        those of an earlier step."""
+        if self._staged != self.launches:
+            raise RuntimeError("ReplayBuffer.add on a ring with a reward source needs the step staged by the "
+                               "RewardVecEnvWrapper the trainer built (stage() was not called for this step)")
+
+    def store_step(self, ring_row: int, obs, next_obs, ring_action, ring_done) -> None:
+        self.require_staged()
+        k, rec = self._slot()
+        n = self.n
+        rec["obs"][...] = np.asarray(obs).reshape(n, -1)
+        rec["next_obs"][...] = np.asarray(next_obs).reshape(n, -1)
+        rec["ring_done"][...] = ring_done
+        if not self.discrete:
+            rec["ring_act"][...] = np.asarray(ring_action).reshape(n, -1)
+        if self.tile_step == self.tile_cap:
+            self._alloc_tile(2 * self.tile_cap)
+        rewards_in = None
+        if self.base is None:   # any other net: its prediction stays on the device
+            so, sa = tuple(self.ring.observation_space.shape), tuple(self.ring.action_space.shape)
+            rewards_in = self.net.predict_th(rec["obs"].reshape((n,) + so), rec["act"].reshape((n,) + sa),
+                                             rec["next_obs"].reshape((n,) + so), rec["dones"].astype(bool)).contiguous()
+        a = self._slot_args(k)
+        if rewards_in is not None:
+            a.rewards_in = rewards_in.data_ptr()
+        a.ring_row, a.tile_row = int(ring_row), self.tile_step * n
+        a.rewards_host = self.rewards_host.data_ptr() + 4 * self.tile_step * n
+        L.check(L.load().ia_offpolicy_step(C.byref(a), L.stream()), "ia_offpolicy_step")
+        if self.events[k] is None:
+            self.events[k] = th.cuda.Event()
+        self.events[k].record()
+        self.last_event = self.events[k]
+        self.launches += 1
+        self.tile_step += 1
+
+    def _slot_args(self, k: int):
+        """The argument record of pinned record `k`; refilled when a buffer it points to has moved (a longer round tile,
+        a reward net moved to another device)."""
+        b = self.base
+        nrm = None if b is None else b.mlp.norm
+        key = (self.tile_obs.data_ptr(), None if b is None else b.mlp.flat.data_ptr(),
+               None if nrm is None else nrm.running_mean.data_ptr())
+        if self._args[k] is not None and self._args[k][0] == key:
+            return self._args[k][1]
+        slot, t, n, a = self.slots[k], self.ring.table, self.n, L.OffpolicyStepArgs()
+        a.obs, a.next_obs = slot["obs"].data_ptr(), slot["next_obs"].data_ptr()
+        a.act_i64 = slot["act"].data_ptr() if self.discrete else None
+        a.act_f32 = None if self.discrete else slot["act"].data_ptr()
+        a.ring_act_f32 = None if self.discrete else slot["ring_act"].data_ptr()
+        a.dones, a.ring_done = slot["dones"].data_ptr(), slot["ring_done"].data_ptr()
+        a.n, a.obs_dim, a.act_dim = n, self.od, self.act_dim
+        if b is not None:
+            a.use_state, a.use_action, a.use_next_state, a.use_done = (int(f) for f in b.flags)
+            a.desc, a.params = C.pointer(b.mlp.desc), b.mlp.flat.data_ptr()
+            a.norm_mean = None if nrm is None else nrm.running_mean.data_ptr()
+            a.norm_var = None if nrm is None else nrm.running_var.data_ptr()
+            a.norm_eps, a.out_act = (0.0 if nrm is None else float(nrm.eps)), self.out_act
+        a.ring_obs, a.ring_next_obs = t.obs.data_ptr(), t.next_obs.data_ptr()
+        a.ring_action_i64 = t.action.data_ptr() if self.discrete else None
+        a.ring_action_f32 = None if self.discrete else t.action.data_ptr()
+        a.ring_reward, a.ring_done_out, a.ring_rows = t.reward.data_ptr(), t.done.data_ptr(), t.rows
+        a.tile_obs, a.tile_next_obs = self.tile_obs.data_ptr(), self.tile_next.data_ptr()
+        a.tile_act_i64 = self.tile_act.data_ptr() if self.discrete else None
+        a.tile_act_f32 = None if self.discrete else self.tile_act.data_ptr()
+        a.tile_dones, a.tile_rows = self.tile_dones.data_ptr(), self.tile_cap * n
+        self._args[k] = (key, a)
+        return a
+
+    def wait(self) -> None:
+        """Until the latest launch has completed (its rewards are then in the pinned tile)."""
+        if self.launches:
+            self.last_event.synchronize()
+
+    def rollout_view(self):
+        """The round tile with the fields `buffer.ReplayBuffer.store_from_rollout` reads."""
+        T, n = self.tile_step, self.n
+        return _RoundTile(self.tile_obs[:(T + 1) * n], self.tile_next[:T * n], self.tile_act[:T * n].reshape(T * n, -1),
+                          self.tile_dones[:T * n], T, n)
+
+    def reset_tile(self) -> None:
+        self.tile_step = 0
+
+
+class _RoundTile(NamedTuple):
+    obs: th.Tensor
+    next_fixed: th.Tensor
+    clipped: th.Tensor
+    dones: th.Tensor
+    buffer_size: int
+    n_envs: int
 
 
 class QNetwork:
@@ -470,6 +658,21 @@ class OffPolicyAlgorithm:
 
     def get_env(self):
         return self.env
+
+    def set_env(self, env, force_reset: bool = True) -> None:
+        """[SB3 BaseAlgorithm.set_env]: the spaces and the number of environments must be the model's; with `force_reset`
+        the next `_setup_learn` resets the environment."""
+        if env.num_envs != self.n_envs:
+            raise ValueError("The number of environments to be set is different from the number of environments in "
+                             f"the model: ({env.num_envs} != {self.n_envs})")
+        if env.observation_space != self.observation_space:
+            raise ValueError(f"Observation spaces do not match: {self.observation_space} != {env.observation_space}")
+        if env.action_space != self.action_space:
+            raise ValueError(f"Action spaces do not match: {self.action_space} != {env.action_space}")
+        if force_reset:
+            self._last_obs = None
+        self.n_envs = env.num_envs
+        self.env = env
 
     def _init_callback(self, callback):
         if callback is None:

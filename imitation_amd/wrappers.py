@@ -207,9 +207,10 @@ class BufferingWrapper(VecEnvWrapper):
 class WrappedRewardCallback:
     """`rewards/reward_wrapper.py:15-37`: logs the mean wrapped episode reward at rollout start."""
 
-    def __init__(self, episode_rewards: Deque[float]):
+    def __init__(self, episode_rewards: Deque[float], flush: Optional[Callable[[], None]] = None):
         self.episode_rewards = episode_rewards
         self.model = None
+        self.flush = flush   # brings a deferred episode bookkeeping up to date before the deque is read
 
     def init_callback(self, model) -> None:
         self.model = model
@@ -218,6 +219,8 @@ class WrappedRewardCallback:
         pass
 
     def on_rollout_start(self) -> None:
+        if self.flush is not None:
+            self.flush()
         if len(self.episode_rewards) == 0:
             return
         mean = sum(self.episode_rewards) / len(self.episode_rewards)
@@ -247,10 +250,16 @@ class RewardVecEnvWrapper(VecEnvWrapper):
         self.reward_fn = reward_fn
         self._old_obs = None
         self._actions = None
+        # `dqn.RewardStepSource` (off-policy generators): `step_wait` then computes no reward -- the learner ring's `add`
+        # relabels and stores the step in one launch -- and the episode bookkeeping is deferred (`flush_rewards`)
+        self.step_source = None
+        self._pending_dones: List[np.ndarray] = []
+        self._flushed_step = 0
+        self.reward_fn_calls = 0     # per-step reward predictions with their read-back (tests count them)
         self.reset()
 
     def make_log_callback(self) -> WrappedRewardCallback:
-        return WrappedRewardCallback(self.episode_rewards)
+        return WrappedRewardCallback(self.episode_rewards, flush=self.flush_rewards)
 
     @property
     def envs(self):
@@ -267,9 +276,21 @@ class RewardVecEnvWrapper(VecEnvWrapper):
     def step_wait(self):
         obs, old_rews, dones, infos = self.venv.step_wait()
         dones = np.asarray(dones, dtype=bool)
+        if self.step_source is not None:
+            # the step's reward is written by the launch behind the learner's `ReplayBuffer.add`: hand back its row of
+            # the pinned reward tile (filled once that launch has completed) and note the dones for `flush_rewards`
+            self.step_source.stage(self._actions, dones)
+            rews = self.step_source.reward_row()
+            del self._pending_dones[self.step_source.tile_step - self._flushed_step:]   # (a staged step never stored)
+            self._pending_dones.append(dones)
+            self._old_obs = obs
+            for info, r in zip(infos, old_rews):
+                info["original_env_rew"] = r
+            return obs, rews, dones, infos
         fixed = np.array(obs, copy=True)
         for i in np.flatnonzero(dones):
             fixed[i] = infos[i]["terminal_observation"]
+        self.reward_fn_calls += 1
         rews = self.reward_fn(self._old_obs, self._actions, fixed, np.array(dones))
         assert len(rews) == len(obs), "must return one rew for each env"
         self.record_rewards(rews[None], dones[None], obs)
@@ -287,3 +308,27 @@ class RewardVecEnvWrapper(VecEnvWrapper):
                 self.episode_rewards.extend(self._cumulative_rew[d].tolist())
                 self._cumulative_rew[d] = 0
         self._old_obs = last_obs
+
+    def flush_rewards(self, force: bool = False) -> None:
+        """The deferred episode bookkeeping of the steps stored since the last flush: `record_rewards` on their rows of
+        the pinned reward tile, behind one event wait. Without `force` it waits only when an episode ended among them
+        (nothing else changes `episode_rewards`)."""
+        src = self.step_source
+        if src is None:
+            return
+        hi = src.tile_step   # (a step that was staged but never stored has no reward: it stays pending)
+        n_new = hi - self._flushed_step
+        if n_new <= 0 or not (force or any(d.any() for d in self._pending_dones[:n_new])):
+            return
+        src.wait()
+        self.record_rewards(src.rewards_np[self._flushed_step:hi], np.stack(self._pending_dones[:n_new]), self._old_obs)
+        del self._pending_dones[:n_new]
+        self._flushed_step = hi
+
+    def end_round(self) -> None:
+        """End of a generator round: everything flushed, the round tile starts over."""
+        if self.step_source is not None:
+            self.flush_rewards(force=True)
+            self._pending_dones = []
+            self.step_source.reset_tile()
+            self._flushed_step = 0

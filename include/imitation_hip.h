@@ -932,6 +932,44 @@ int ia_td3_actor_input(const float* mu, int B, int D, int A, int ld, float* X, v
 int ia_td3_actor_seed(const float* q1, const float* dX, const float* mu, int B, int D, int A, int ld, float* dmu, float* loss,
                       void* stream);
 
+/* ---- one environment step of an off-policy generator under a learned reward (csrc/offpolicy.hip) ------------------
+ * ONE launch: the step's n transitions are relabelled with the discriminator's reward and stored to the learner's replay
+ * table, to the trainer's per-round tile and to a pinned host array of rewards. The step's rows (obs, next_obs, the two
+ * actions, dones, ring_done) may live in pinned (device-mapped) host memory or in device memory.
+ *   act_i64 / act_f32: the action the discriminator sees, exactly one non-NULL: int64 [n] (Discrete, one-hot to act_dim
+ *                     in the kernel) or float32 [n, act_dim] (Box);
+ *   ring_act_f32:     Box only: the action the learner's table receives (SB3's scaled action); NULL: act_f32;
+ *   dones:            raw uint8 [n], for the discriminator and the tile; ring_done: float32 [n], what the table receives
+ *                     (done * (1 - timeout), formed by the caller);
+ *   desc != NULL:     reward = out_act(stack([state | action | next_state | done] by the use_* flags)), inputs normalised
+ *                     as (x - mean) * (1 / sqrt(var + eps)) when norm_mean / norm_var are given; D <= 64 -> 32 -> 32 -> 1
+ *                     ReLU stacks only (the predicate below), any other IA_ERR_UNSUPPORTED;
+ *   desc == NULL:     reward = rewards_in[n] (device memory);
+ *   ring_*:           rows ring_row .. ring_row + n - 1 of the table ([ring_rows, obs_dim] twice, int64 [ring_rows] or
+ *                     float32 [ring_rows, act_dim], reward and done float32 [ring_rows]); ring_row + n <= ring_rows is
+ *                     checked here (IA_ERR_ARG, nothing is written);
+ *   tile_*:           all NULL, or rows tile_row .. tile_row + n - 1 of a [tile_rows] tile receive (obs, the
+ *                     discriminator's action, next_obs, raw done);
+ *   rewards_host:     NULL, or the n rewards (pinned host memory).
+ * A row's reward depends on neither the other rows nor n; every sum has a fixed order; no atomics. One workgroup takes
+ * ia_offpolicy_step_rows rows. */
+typedef struct {
+  const float* obs; const float* next_obs; const int64_t* act_i64; const float* act_f32; const float* ring_act_f32;
+  const uint8_t* dones; const float* ring_done;
+  int n, obs_dim, act_dim, use_state, use_action, use_next_state, use_done;
+  const ia_mlp_desc* desc; const float* params; const float* norm_mean; const float* norm_var; float norm_eps; int out_act;
+  const float* rewards_in;
+  float* ring_obs; float* ring_next_obs; int64_t* ring_action_i64; float* ring_action_f32; float* ring_reward;
+  float* ring_done_out; int64_t ring_row, ring_rows;
+  float* tile_obs; float* tile_next_obs; int64_t* tile_act_i64; float* tile_act_f32; uint8_t* tile_dones;
+  int64_t tile_row, tile_rows;
+  float* rewards_host;
+} ia_offpolicy_step_args;
+int ia_offpolicy_step_rows(void);
+int ia_offpolicy_step_ok(const ia_mlp_desc* d, int obs_dim, int act_dim, int use_state, int use_action, int use_next_state,
+                         int use_done);
+int ia_offpolicy_step(const ia_offpolicy_step_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
