@@ -263,6 +263,8 @@ _SIGS = {
     "ia_pref_loss": ([_P, _P, _I, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P], C.c_int),
     "ia_pref_frag_moments": ([_P, _I, _I, _I, _I, _L, _P, _P], C.c_int),
     "ia_pref_norm_apply_seq": ([_P, _I, _I, _I, _I, _P, _F, _P, _I, _P], C.c_int),
+    "ia_pref_gather_frames": ([_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
+    "ia_pref_gather_frames_lut": ([_P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], C.c_int),
     "ia_adamw_step": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P], C.c_int),
     "ia_reduce_partials_adamw": ([_P, _I, _L, _F, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P], C.c_int),
     "ia_mce_backup": ([_P, _P, _I, _I, _I, _D, _P, _P, _P, _P], C.c_int),

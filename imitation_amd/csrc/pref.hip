@@ -186,6 +186,141 @@ __global__ void reduce_adamw_kernel(const float* __restrict__ partials, int spli
 
 inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }
 
+// ---- frame gather: uint8 frame table -> fp32 channel-last CNN input -------------------------------------------------
+// One workgroup per tile = (row r, pixels [p0, p0 + tp)). The tile's source bytes are `n_spans` contiguous runs ("spans"):
+// table [F, H, W, C]: one per source frame, tp * C bytes; table [F, C, H, W]: one per (source frame, channel), tp bytes.
+// Phase 1 copies the spans into LDS, each at the LDS offset congruent to its global address mod 16, so every 16-byte slot
+// that lies wholly inside a span moves with one aligned 16-byte load and one 16-byte LDS store; the slots a span only
+// partly covers (its unaligned head and tail) move byte by byte. No byte outside a span is read. Phase 2: a lane forms
+// four consecutive floats of X from LDS bytes (for the [F, C, H, W] table this is the transpose: a pixel's channels are
+// `span_stride` apart in LDS) and stores them as one aligned 16-byte vector; the floats of a tile before the first / after
+// the last 16-byte boundary are stored one by one.
+constexpr int GF_THREADS = 256;
+constexpr int GF_LDS = 16384;         // staged bytes of one tile, the spans' padding included
+constexpr int GF_MAX_SPANS = 256;
+constexpr int GF_TILE_ELEMS = 8192;   // output floats of one tile, at most
+
+struct GatherFrames {
+  const uint8_t* frames;
+  long long n_frames;
+  const long long* idx;
+  const float* lut;     // nullable: 256 floats, the value of every byte
+  float* X;
+  int HW, C, S, base;   // pixels per frame, channels per frame, source frames per row (1 or 2), first source = idx + base
+  int chw;              // table layout [F, C, H, W]
+  int TP, tiles_per_row, n_spans, span_stride;
+};
+
+__global__ __launch_bounds__(GF_THREADS) void pref_gather_frames_kernel(const GatherFrames g) {
+  __shared__ __attribute__((aligned(16))) unsigned char stage[GF_LDS];
+  __shared__ int span_off[GF_MAX_SPANS];
+  __shared__ float lut[256];
+  const int tid = threadIdx.x;
+  const int r = blockIdx.x / g.tiles_per_row, tile = blockIdx.x - r * g.tiles_per_row;
+  const int p0 = tile * g.TP, tp = min(g.TP, g.HW - p0);
+  const int Cin = g.C * g.S;
+  const long long N = (long long)g.HW * g.C;
+  const long long f0 = g.idx[r] + g.base;
+  float* xt = g.X + ((long long)r * g.HW + p0) * Cin;   // the tile's first float
+  const int n_out = tp * Cin;
+  if (f0 < 0 || f0 + g.S > g.n_frames) {   // a row outside the table reads nothing and is loud downstream
+    for (int e = tid; e < n_out; e += GF_THREADS) xt[e] = __builtin_nanf("");
+    return;
+  }
+  const int span_len = g.chw ? tp : tp * g.C;
+  auto span_src = [&](int j) -> const uint8_t* {
+    if (g.chw) {
+      const int s = j / g.C, c = j - s * g.C;
+      return g.frames + (f0 + s) * N + (long long)c * g.HW + p0;
+    }
+    return g.frames + (f0 + j) * N + (long long)p0 * g.C;
+  };
+  if (g.lut != nullptr) lut[tid] = g.lut[tid];
+  for (int j = tid; j < g.n_spans; j += GF_THREADS)
+    span_off[j] = j * g.span_stride + (int)((uintptr_t)span_src(j) & 15);
+  const int slots = g.span_stride >> 4;
+  for (int it = tid; it < g.n_spans * slots; it += GF_THREADS) {
+    const int j = it / slots, v = it - j * slots;
+    const uintptr_t lo = (uintptr_t)span_src(j), hi = lo + (uintptr_t)span_len;
+    const uintptr_t a = (lo & ~(uintptr_t)15) + 16u * (uintptr_t)v;   // the slot's global address (16-byte aligned)
+    unsigned char* dst = stage + j * g.span_stride + 16 * v;
+    if (a >= lo && a + 16 <= hi) {
+      *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(a);
+    } else if (a + 16 > lo && a < hi) {
+      for (int b = 0; b < 16; ++b)
+        if (a + b >= lo && a + b < hi) dst[b] = *reinterpret_cast<const uint8_t*>(a + b);
+    }
+  }
+  __syncthreads();
+  auto value = [&](int p, int ci) -> float {
+    const int s = ci >= g.C ? 1 : 0;
+    const int at = g.chw ? span_off[ci] + p : span_off[s] + p * g.C + (ci - s * g.C);
+    const unsigned b = stage[at];
+    return g.lut != nullptr ? lut[b] : (float)b / 255.0f;
+  };
+  const int mis = (int)(((uintptr_t)xt >> 2) & 3);   // floats between the last 16-byte boundary and the tile's first
+  const int nq = (mis + n_out + 3) >> 2;
+  const bool quads = (Cin & 3) == 0 && mis == 0;     // every vector lies inside one pixel
+  for (int q = tid; q < nq; q += GF_THREADS) {
+    const int e0 = 4 * q - mis;
+    if (quads) {
+      const int p = e0 / Cin, ci = e0 - p * Cin;
+      const f32x4 o = {value(p, ci), value(p, ci + 1), value(p, ci + 2), value(p, ci + 3)};
+      *reinterpret_cast<f32x4*>(xt + e0) = o;
+    } else if (e0 >= 0 && e0 + 4 <= n_out) {
+      f32x4 o;
+      for (int k = 0; k < 4; ++k) {
+        const int p = (e0 + k) / Cin;
+        o[k] = value(p, e0 + k - p * Cin);
+      }
+      *reinterpret_cast<f32x4*>(xt + e0) = o;
+    } else {
+      for (int k = 0; k < 4; ++k) {
+        const int e = e0 + k;
+        if (e < 0 || e >= n_out) continue;
+        const int p = e / Cin;
+        xt[e] = value(p, e - p * Cin);
+      }
+    }
+  }
+}
+
+int launch_gather_frames(const uint8_t* frames, long long n_frames, const int64_t* frame_idx, int n_rows, int H, int W,
+                         int C, int table_chw, int use_state, int use_next, const float* lut, float* X, void* stream) {
+  const int S = (use_state != 0) + (use_next != 0);
+  if (frames == nullptr || frame_idx == nullptr || X == nullptr) return IA_ERR_ARG;
+  if (S == 0 || n_rows <= 0 || H <= 0 || W <= 0 || C <= 0 || n_frames <= 0) return IA_ERR_ARG;
+  const long long HW = (long long)H * W;
+  if (HW * C * S > (1LL << 30)) return IA_ERR_UNSUPPORTED;   // a row's float count stays a 32-bit index
+  GatherFrames g;
+  g.frames = frames;
+  g.n_frames = n_frames;
+  g.idx = reinterpret_cast<const long long*>(frame_idx);
+  g.lut = lut;
+  g.X = X;
+  g.HW = (int)HW;
+  g.C = C;
+  g.S = S;
+  g.base = use_state ? 0 : 1;
+  g.chw = table_chw != 0;
+  g.n_spans = g.chw ? S * C : S;
+  if (g.n_spans > GF_MAX_SPANS) return IA_ERR_UNSUPPORTED;
+  const int unit = g.chw ? 1 : C;                              // bytes of a pixel inside one span
+  const int max_len = ((GF_LDS / g.n_spans) & ~15) - 16;       // a span's bytes; 16 more hold its misalignment
+  if (max_len < unit) return IA_ERR_UNSUPPORTED;
+  long long TP = max_len / unit;
+  TP = TP < GF_TILE_ELEMS / (C * S) ? TP : GF_TILE_ELEMS / (C * S);
+  TP = TP < 1 ? 1 : (TP > HW ? HW : TP);
+  g.TP = (int)TP;
+  g.span_stride = (g.TP * unit + 15) / 16 * 16 + 16;
+  g.tiles_per_row = (int)cdivl(HW, TP);
+  const long long grid = (long long)n_rows * g.tiles_per_row;
+  if (grid > 0x7fffffffLL) return IA_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(pref_gather_frames_kernel, dim3((unsigned)grid), dim3(GF_THREADS), 0, (hipStream_t)stream, g);
+  IA_CHECK_LAUNCH();
+  return IA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -220,6 +355,19 @@ int ia_pref_norm_apply_seq(const float* X, int ldx, int n_frags, int L, int D, c
                      ldx, n_frags, L, D, snapshots, eps, Y, ldy);
   IA_CHECK_LAUNCH();
   return IA_OK;
+}
+
+int ia_pref_gather_frames(const uint8_t* frames, const int64_t* frame_idx, int n_rows, int H, int W, int C, int table_chw,
+                          int use_state, int use_next, float* X, void* stream) {
+  return launch_gather_frames(frames, INT64_MAX, frame_idx, n_rows, H, W, C, table_chw, use_state, use_next, nullptr, X,
+                              stream);
+}
+
+int ia_pref_gather_frames_lut(const uint8_t* frames, int64_t n_frames, const int64_t* frame_idx, int n_rows, int H, int W,
+                              int C, int table_chw, int use_state, int use_next, const float* lut, float* X,
+                              void* stream) {
+  return launch_gather_frames(frames, n_frames, frame_idx, n_rows, H, W, C, table_chw, use_state, use_next, lut, X,
+                              stream);
 }
 
 int ia_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,

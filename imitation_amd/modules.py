@@ -305,7 +305,11 @@ class Cnn(nn.Module):
         self.dims_final = [prev, int(out_size)]
 
     def forward(self, x: th.Tensor) -> th.Tensor:
-        h = x.permute(0, 2, 3, 1).contiguous()                  # [B, C, H, W] -> channel-last
+        return self.forward_nhwc(x.permute(0, 2, 3, 1).contiguous())   # [B, C, H, W] -> channel-last
+
+    def forward_nhwc(self, h: th.Tensor) -> th.Tensor:
+        """`forward` from an input that is channel-last already (`[B, H, W, C]`, contiguous fp32): the one body of the
+        arithmetic; `forward` only adds the layout copy in front."""
         # every layer's ReLU backward rides in the NEXT layer's input-gradient epilogue (`ops.conv2d_nhwc`)
         for i, n in enumerate(self._convs[:-1]):
             conv = getattr(self, n)
@@ -358,10 +362,18 @@ class CnnRewardNet(RewardNet):
         images = [t for on, t in ((self.use_state, state), (self.use_next_state, next_state)) if on]
         if self.hwc_format:   # [B, H, W, C] frames: channel-first for the CNN's input contract
             images = [t.permute(0, 3, 1, 2) for t in images]
-        out = self.cnn(th.cat(images, dim=1))
+        return self._select(self.cnn(th.cat(images, dim=1)), action, done)
+
+    def forward_nhwc(self, x_nhwc: th.Tensor, action: th.Tensor, done: th.Tensor) -> th.Tensor:
+        """`forward` from the CNN's assembled input: `x_nhwc[B, H, W, C * (use_state + use_next_state)]`, channel-last,
+        the state's channels first, scaled like `preprocess` scales them (`ops.pref_gather_frames` writes this from a
+        uint8 frame table). Same action / done selection, same arithmetic as `forward`."""
+        return self._select(self.cnn.forward_nhwc(x_nhwc), action, done)
+
+    def _select(self, out: th.Tensor, action: th.Tensor, done: th.Tensor) -> th.Tensor:
         if not self.use_action and not self.use_done:
             return out
-        n = state.shape[0]
+        n = out.shape[0]
         if self.use_action:
             sel = action.reshape(n, -1).float()
             if self.use_done:   # first half of the outputs: done = False, second half: done = True

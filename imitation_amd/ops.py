@@ -564,6 +564,47 @@ def preference_loss(rewards: Tensor, pair_off: Tensor, prefs: Tensor, gt_rewards
                            float(discount_factor), float(noise_prob), float(threshold))
 
 
+_byte_luts: dict = {}
+
+
+def _byte_lut(device: th.device) -> Tensor:
+    """`x.float() / 255.0` of the 256 byte values, formed once per device by torch's own kernel (`preprocess_space`'s
+    expression): what `pref_gather_frames` writes, so its output and `preprocess`ed frames agree bit for bit whichever
+    way that kernel divides."""
+    key = (device.type, device.index if device.index is not None else th.cuda.current_device())
+    if key not in _byte_luts:
+        _byte_luts[key] = (th.arange(256, dtype=th.uint8, device=device).float() / 255.0).contiguous()
+    return _byte_luts[key]
+
+
+@th.library.custom_op("imitation_amd::pref_gather_frames", mutates_args=(), device_types="cuda")
+def pref_gather_frames(frames: Tensor, frame_idx: Tensor, use_state: bool, use_next: bool, table_chw: bool) -> Tensor:
+    """The reward CNN's channel-last input `[n, H, W, C * (use_state + use_next)]` (fp32) of the rows whose state frame is
+    `frame_idx[r]` and whose next-state frame is `frame_idx[r] + 1` in the uint8 table `frames` (`[F, H, W, C]`, or
+    `[F, C, H, W]` with `table_chw`): state channels first, every value `byte / 255` (`ia_pref_gather_frames_lut`). No
+    gradient: frames are data. A row whose frames are not in the table comes back as NaN."""
+    if not frames.is_cuda:
+        raise RuntimeError(f"imitation_amd ops compute on MI355X only (no CPU fallback): `frames` is on {frames.device}")
+    if frames.dtype != th.uint8 or frames.dim() != 4 or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous uint8 tensor [F, H, W, C] or [F, C, H, W]")
+    if frame_idx.dtype != th.int64 or frame_idx.dim() != 1:
+        raise ValueError("frame_idx must be an int64 vector")
+    F = frames.shape[0]
+    (Cc, H, W) = frames.shape[1:] if table_chw else (frames.shape[3], frames.shape[1], frames.shape[2])
+    n = frame_idx.numel()
+    X = th.empty(n, H, W, Cc * (int(use_state) + int(use_next)), device=frames.device)
+    if n:
+        L.call("ia_pref_gather_frames_lut", L.ptr(frames), F, L.ptr(frame_idx.contiguous()), n, H, W, Cc, int(table_chw),
+               int(use_state), int(use_next), L.ptr(_byte_lut(frames.device)), L.ptr(X), L.stream())
+    return X
+
+
+@pref_gather_frames.register_fake
+def _(frames, frame_idx, use_state, use_next, table_chw):
+    (Cc, H, W) = frames.shape[1:] if table_chw else (frames.shape[3], frames.shape[1], frames.shape[2])
+    return frames.new_empty(frame_idx.numel(), H, W, Cc * (int(use_state) + int(use_next)), dtype=th.float32)
+
+
 @th.library.custom_op("imitation_amd::adamw_step", mutates_args=("p", "m", "v"), device_types="cuda")
 def adamw_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, beta1: float, beta2: float, eps: float, decay: float,
                step_size: float, bc2_sqrt: float) -> None:

@@ -11,7 +11,13 @@ The host side keeps the reference's constructors, defaults, errors, RNG draws an
   `ia_adamw_step`). No host synchronisation between minibatches; the statistics are read back once per call and
   replayed into the logger;
 * a product `BasicShapedRewardNet` without input normalisation: its shaped forward, `ia_pref_loss` and its backward;
-* a `modules.RewardNet` (`nn.Module`): its own forward with autograd, `ops.preference_loss`, `ops.HipAdamW`.
+* a `modules.RewardNet` (`nn.Module`): its own forward with autograd, `ops.preference_loss`, `ops.HipAdamW`;
+* image fragments (uint8 observations with three trailing dimensions) under an `nn.Module` net: the frames live once, as
+  uint8, in a device `_FrameTable`; a minibatch is one vector of state-frame indices (the next state is the frame behind
+  it). A `modules.CnnRewardNet` (also under `PredictProcessedWrapper`s such as `NormalizedRewardNet`) takes its
+  channel-last input from one `ops.pref_gather_frames` launch (`ia_pref_gather_frames`: gather, `/ 255`, the channel
+  concatenation and the layout in one pass) through `CnnRewardNet.forward_nhwc`; any other `nn.Module` net gets state and
+  next-state tensors in the space's layout from two launches and runs its own `forward`.
 
 Out of scope here (each raises `NotImplementedError`): `ActiveSelectionFragmenter`, reward ensembles, regularizers and
 exploration in `AgentTrainer`.
@@ -418,11 +424,89 @@ class PreferenceDataset:
         with open(path, "rb") as file:
             return pickle.load(file)
 
-    def device_table(self, device, discrete: bool) -> "_FragmentTable":
+    def device_table(self, device, discrete: bool, frames: bool = True) -> Union["_FragmentTable", "_FrameTable"]:
+        """The device mirror: a `_FrameTable` when the fragments hold uint8 images (and the caller can read one:
+        `frames`), else the flat fp32 `_FragmentTable`."""
+        cls = _FrameTable if frames and _holds_image_fragments(self) else _FragmentTable
         m = self._mirror
-        if m is None or m.device != th.device(device) or m.discrete != discrete:
-            m = self._mirror = _FragmentTable(self, th.device(device), discrete)
+        if m is None or type(m) is not cls or m.device != th.device(device) or m.discrete != discrete:
+            m = self._mirror = cls(self, th.device(device), discrete)
         return m
+
+
+def _holds_image_fragments(ds: PreferenceDataset) -> bool:
+    """Observations of the image space of `modules._is_image_space`: uint8 arrays with three trailing dimensions."""
+    if not len(ds):
+        return False
+    obs = ds.fragments1[0].obs
+    return isinstance(obs, np.ndarray) and obs.dtype == np.uint8 and obs.ndim == 4
+
+
+def frame_table_index(pair_len: np.ndarray, pairs: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Index arithmetic of `_FrameTable` (NumPy only). The table holds, pair by pair, fragment 1's `L + 1` frames and then
+    fragment 2's, `L = pair_len[pair]`. Returns, for the pairs `pairs` in batch order (per pair: fragment 1's steps, then
+    fragment 2's), the state-frame index of every row -- step t of a fragment whose first frame is f0 reads frame f0 + t,
+    its next state is frame f0 + t + 1 -- and the pair offsets [P + 1] in steps."""
+    pair_len = np.asarray(pair_len, np.int64)
+    frag_start = np.zeros(2 * len(pair_len) + 1, dtype=np.int64)
+    np.cumsum(np.repeat(pair_len + 1, 2), out=frag_start[1:])
+    lens = pair_len[pairs]
+    off = np.zeros(len(pairs) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    idx = [np.arange(frag_start[2 * p + k], frag_start[2 * p + k] + l) for p, l in zip(pairs, lens) for k in (0, 1)]
+    return (np.concatenate(idx) if idx else np.zeros(0, np.int64)), off
+
+
+def frame_table_arrays(ds: PreferenceDataset, discrete: bool) -> Dict[str, np.ndarray]:
+    """The host arrays of `_FrameTable` (NumPy only), every one indexed by frame: `frames` uint8 `[F, *obs shape]` in the
+    observation space's layout, and per state frame the action, the done flag and the ground-truth reward of the step that
+    starts there (the entry at a fragment's last frame, where no step starts, is zero and never read)."""
+    lens = np.array([len(f) for f in ds.fragments1], dtype=np.int64)
+    if any(len(f2) != l for f2, l in zip(ds.fragments2, lens)):
+        raise ValueError("the two fragments of a pair must have the same length")
+    frags = [f for pair in zip(ds.fragments1, ds.fragments2) for f in pair]
+    has_gt = bool(len(ds)) and _trajectory_pair_includes_reward(ds[0][0])
+    pad = lambda a: np.concatenate([a, np.zeros((1,) + a.shape[1:], a.dtype)])
+    if discrete:
+        acts = [pad(np.asarray(f.acts, np.int64).reshape(-1)) for f in frags]
+    else:
+        acts = [pad(np.asarray(f.acts, np.float32).reshape(len(f), -1)) for f in frags]
+    dones = []
+    for f in frags:
+        d = np.zeros(len(f) + 1, np.uint8)
+        d[len(f) - 1] = f.terminal       # `flatten_trajectories`: only a terminal fragment's last step is done
+        dones.append(d)
+    gt = [pad(np.asarray(f.rews, np.float32)) if has_gt else np.zeros(len(f) + 1, np.float32) for f in frags]
+    frames = np.ascontiguousarray(np.concatenate([np.asarray(f.obs) for f in frags]))
+    return {"frames": frames, "acts": np.concatenate(acts), "dones": np.concatenate(dones), "gt": np.concatenate(gt),
+            "pair_len": lens, "has_gt": has_gt}
+
+
+class _FrameTable:
+    """Image fragments on the device: every frame stored ONCE, as uint8, in the observation space's layout (`[F, H, W, C]`,
+    or `[F, C, H, W]` for a channel-first space). A fragment of L steps holds L + 1 frames; step t reads frame f0 + t as
+    state and frame f0 + t + 1 as next state (`frame_table_index`), so a minibatch is described by one index vector and
+    `ops.pref_gather_frames` builds the CNN's input from it. Actions (int64 for a Discrete space), dones and ground-truth
+    rewards are indexed by the state frame too. Pairs are laid out as in `_FragmentTable`: fragment 1, then fragment 2.
+    Device bytes of the frames: F * H * W * C with F = sum over fragments of (L + 1); `_FragmentTable` holds
+    2 * R * H * W * C * 4 for the same R = sum of L transitions (state and next state, fp32): 8 L / (L + 1) times as
+    many, 7.3 x at L = 10."""
+
+    def __init__(self, ds: PreferenceDataset, device: th.device, discrete: bool):
+        self.device, self.discrete = device, discrete
+        a = frame_table_arrays(ds, discrete)
+        self.pair_len = a["pair_len"]
+        self.frames = th.as_tensor(a["frames"]).to(device).contiguous()
+        self.acts = th.as_tensor(a["acts"]).to(device).contiguous()
+        self.dones = th.as_tensor(a["dones"]).to(device).contiguous()
+        self.gt = th.as_tensor(a["gt"]).to(device)
+        self.prefs = np.asarray(ds.preferences, np.float32)
+        self.has_gt = a["has_gt"]
+
+    def batch(self, pairs: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(state-frame index of every row in batch order, pair offsets [P+1] in steps) of the pairs `pairs`; a row's
+        next-state frame is its state frame + 1."""
+        return frame_table_index(self.pair_len, pairs)
 
 
 class _FragmentTable:
@@ -612,6 +696,14 @@ def _as_basic(model):
     return m if type(m) is reward_nets.BasicRewardNet else None
 
 
+def _as_cnn(model):
+    """The `modules.CnnRewardNet` whose forward `model`'s forward is (through `PredictProcessedWrapper`s), or None."""
+    m = model
+    while isinstance(m, modules.PredictProcessedWrapper):
+        m = m.base
+    return m if type(m) is modules.CnnRewardNet else None
+
+
 class _PairBatchRunner:
     """Forward, loss, backward and optimiser steps of minibatches of fragment pairs; the path is chosen from the net's
     type: "basic" (product `BasicRewardNet`), "shaped" (product `ShapedRewardNet`) or "module" (`nn.Module`)."""
@@ -647,7 +739,7 @@ class _PairBatchRunner:
 
     # -- one minibatch's loss on the device: (loss tensor for autograd or None, stats[3] device view)
     def loss(self, ds: PreferenceDataset, pairs: np.ndarray):
-        tab = ds.device_table(self.device, self._discrete())
+        tab = ds.device_table(self.device, self._discrete(), frames=self.kind == "module")
         rows, off = tab.batch(pairs)
         rows_d = th.as_tensor(rows).to(self.device)
         off_d = th.as_tensor(off.astype(np.int32)).to(self.device)
@@ -672,9 +764,38 @@ class _PairBatchRunner:
         """The module net's rewards of the rows, one call per fragment like `PreferenceModel.rewards` when the net holds a
         normalisation layer (its statistics move per call), else one call for all rows."""
         model = self.pm.model
+        if isinstance(tab, _FrameTable):
+            return self._frame_rewards(tab, rows_d, off)
         t = tab.table
         acts = t.acts[rows_d]
         s, a, ns, d = model.preprocess(t.obs[rows_d], acts, t.next_obs[rows_d], t.dones[rows_d].bool())
+        if not any(isinstance(m, modules.RunningNorm) for m in model.modules()):
+            return model(s, a, ns, d).reshape(-1)
+        out, r = [], 0
+        for p in range(len(off) - 1):
+            Lp = int(off[p + 1] - off[p])
+            for _ in range(2):
+                out.append(model(s[r:r + Lp], a[r:r + Lp], ns[r:r + Lp], d[r:r + Lp]).reshape(-1))
+                r += Lp
+        return th.cat(out)
+
+    def _frame_rewards(self, tab: "_FrameTable", idx_d: th.Tensor, off: np.ndarray) -> th.Tensor:
+        """Rewards of image rows from the frame table (`idx_d`: their state frames). A `modules.CnnRewardNet` (innermost,
+        under `PredictProcessedWrapper`s) takes its channel-last input from one `ops.pref_gather_frames` launch; any other
+        net goes through its own `forward` on state / next-state tensors in the space's layout (two launches; each
+        fragment in a call of its own when the net holds a normalisation layer, as for flat rows)."""
+        model = self.pm.model
+        if not model.normalize_images:
+            raise NotImplementedError("the frame table scales images by 1 / 255: normalize_images=False is not implemented")
+        a = reward_nets.preprocess_space(tab.acts[idx_d], model.action_space, model.normalize_images)
+        d = tab.dones[idx_d].to(th.float32)
+        cnn = _as_cnn(model)
+        if cnn is not None:
+            x = ops.pref_gather_frames(tab.frames, idx_d, cnn.use_state, cnn.use_next_state, not cnn.hwc_format)
+            return cnn.forward_nhwc(x, a, d).reshape(-1)
+        # read as [F, H, W, C] with one source frame, the op's output has the table's own layout: the space's
+        s = ops.pref_gather_frames(tab.frames, idx_d, True, False, False)
+        ns = ops.pref_gather_frames(tab.frames, idx_d + 1, True, False, False)
         if not any(isinstance(m, modules.RunningNorm) for m in model.modules()):
             return model(s, a, ns, d).reshape(-1)
         out, r = [], 0
@@ -745,7 +866,7 @@ class _PairBatchRunner:
     # -- a whole train call
     def run(self, ds: PreferenceDataset, sched, optim, host_stepped: bool = False) -> np.ndarray:
         dev = self.device
-        tab = ds.device_table(dev, self._discrete())
+        tab = ds.device_table(dev, self._discrete(), frames=self.kind == "module")
         self.has_gt = tab.has_gt
         n_mb = len(sched)
         # every minibatch's rows, pair offsets and preferences in one upload

@@ -842,6 +842,26 @@ int ia_pref_frag_moments(const float* X, int ldx, int n_frags, int L, int D, int
 /* ia_running_norm_apply with fragment f's own statistics: snapshots [n_frags][2][D] (ia_running_norm_merge_seq's). */
 int ia_pref_norm_apply_seq(const float* X, int ldx, int n_frags, int L, int D, const float* snapshots, float eps,
                            float* Y, int ldy, void* stream);
+/* Reward-model input of image fragments (rewards/reward_nets.py:460-610 behind PreferenceModel.rewards :457-489): gathers
+ * rows of a uint8 frame table into the CNN's channel-last fp32 input in ONE launch -- the gather, preprocess_obs'
+ * x.float() / 255, CnnRewardNet.forward's permute + th.cat(images, dim=1) and the channel-last copy in front of the first
+ * convolution.
+ *   frames:    uint8 [F, H, W, C] (table_chw = 0) or [F, C, H, W] (table_chw = 1), frames H*W*C bytes apart, any alignment;
+ *   frame_idx: int64 [n_rows], the STATE frame of every row; the next state is frame frame_idx[r] + 1;
+ *   X:         fp32 [n_rows, H, W, Cin], Cin = C * (use_state + use_next): the C channels of frame frame_idx[r] (use_state),
+ *              then those of frame frame_idx[r] + 1 (use_next); X[.] = (float)byte / 255.0f, IEEE division.
+ * Reads only bytes of the frames it gathers: 16-byte loads where a 16-byte-aligned piece lies wholly inside the bytes a
+ * tile needs, single bytes at unaligned starts and ends; X is written with 16-byte stores (single floats next to a row
+ * boundary that is no multiple of 16 bytes). IA_ERR_ARG for use_state + use_next == 0 or non-positive sizes;
+ * IA_ERR_UNSUPPORTED for more than 256 (frame, channel) planes per row with table_chw = 1.
+ * ia_pref_gather_frames_lut: the same with the table's frame count (a row whose frames are not all inside [0, n_frames)
+ * reads nothing and receives NaN) and, when `lut` is not NULL, X[.] = lut[byte] (256 device floats) instead of the
+ * division: torch's device kernel for `x / 255.0` may multiply by a rounded reciprocal, which differs from the division in
+ * 126 of the 256 values; a table filled by that kernel reproduces it bit for bit. */
+int ia_pref_gather_frames(const uint8_t* frames, const int64_t* frame_idx, int n_rows, int H, int W, int C, int table_chw,
+                          int use_state, int use_next, float* X, void* stream);
+int ia_pref_gather_frames_lut(const uint8_t* frames, int64_t n_frames, const int64_t* frame_idx, int n_rows, int H, int W,
+                              int C, int table_chw, int use_state, int use_next, const float* lut, float* X, void* stream);
 /* torch.optim.AdamW step (decoupled weight decay): params *= decay (= 1 - lr * weight_decay), then ia_adam_step's update
  * with weight_decay = 0. ia_reduce_partials_adamw: grads = scale * sum of the slabs (ia_reduce_partials, accumulate = 0),
  * then the same step -- one launch. */
