@@ -23,13 +23,14 @@ from imitation_amd.adversarial.gail import GAIL, RewardNetFromDiscriminatorLogit
 from imitation_amd.adversarial.airl import AIRL  # noqa: F401
 from imitation_amd.density import DensityAlgorithm, DensityType  # noqa: F401
 from imitation_amd import (bc, checkpoint, cnn_policy, dagger, density, dqn, mce_irl, modules, ops,  # noqa: F401
-                           preference_comparisons, rollout, serialize, sqil, td3)
+                           preference_comparisons, rollout, sac, serialize, sqil, td3)
 from imitation_amd.dagger import (DAggerTrainer, ExponentialBetaSchedule, InteractiveTrajectoryCollector,  # noqa: F401
                                   LinearBetaSchedule, NeedsDemosException, SimpleDAggerTrainer)
 from imitation_amd.mce_irl import MCEIRL, TabularPolicy  # noqa: F401
 from imitation_amd.dqn import DQN, DQNPolicy, QNetwork  # noqa: F401
 from imitation_amd.sqil import SQIL, SQILReplayBuffer  # noqa: F401
 from imitation_amd.td3 import DDPG, TD3, Actor, ContinuousCritic, NormalActionNoise, TD3Policy  # noqa: F401
+from imitation_amd.sac import SAC, SACPolicy  # noqa: F401
 
 
 def configure_logger(folder=None, format_strs=None):

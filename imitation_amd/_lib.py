@@ -283,6 +283,11 @@ _SIGS = {
     "ia_td3_critic_loss": ([_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P], C.c_int),
     "ia_td3_actor_input": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
     "ia_td3_actor_seed": ([_P, _P, _P, _I, _I, _I, _I, _P, _P, _P], C.c_int),
+    "ia_sac_sample": ([_P, _P, _P, _I, _I, _I, _I] + [_P] * 7, C.c_int),
+    "ia_sac_alpha_step": ([_P, _I, _F, _P, _P, _P, _D, _D, _F, _F, _F, _P, _P, _P], C.c_int),
+    "ia_sac_critic_loss": ([_P] * 6 + [_I, _I, _F] + [_P] * 5, C.c_int),
+    "ia_sac_min_seed": ([_P, _I, _I, _P, _P, _P, _P], C.c_int),
+    "ia_sac_actor_seed": ([_P, _P, _I, _I] + [_P] * 8 + [_I, _I, _P, _P, _P], C.c_int),
     "ia_offpolicy_step_rows": ([], C.c_int),
     "ia_offpolicy_step_ok": ([C.POINTER(MlpDesc), _I, _I, _I, _I, _I, _I], C.c_int),
     "ia_offpolicy_step": ([C.POINTER(OffpolicyStepArgs), _P], C.c_int),

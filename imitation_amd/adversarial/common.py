@@ -26,7 +26,7 @@ from imitation_amd import _lib as L
 from imitation_amd import buffer, data_types as dt
 from imitation_amd import dqn
 from imitation_amd import logger as imit_logger
-from imitation_amd import networks, ppo, reward_nets, wrappers
+from imitation_amd import networks, ppo, reward_nets, sac, wrappers
 from imitation_amd.networks import HipAdam, TransitionTable, require_device
 from imitation_amd.policies import ActorCriticPolicy
 
@@ -126,6 +126,9 @@ class AdversarialTrainer(abc.ABC):
         self._ppo_done_event = None
         if isinstance(gen_algo, ppo.PPO):
             gen_algo.randint_spec_for_round = self._replay_rows_spec
+        if isinstance(gen_algo, sac.SAC):
+            raise NotImplementedError("a SAC generator is not implemented for the adversarial trainers yet: SAC runs under "
+                                      "SQIL only (DESIGN section 4.12); use PPO, DQN, TD3 or DDPG as gen_algo")
         self._device = th.device(gen_algo.device)
         require_device(self._device)
         L.load()  # fail loudly here if the HIP extension is missing

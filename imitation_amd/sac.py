@@ -1,0 +1,482 @@
+"""SAC, the stochastic continuous-action learner SQIL can run on (`algorithms/sqil.py:42,77-83`; the reference's tutorial
+`docs/tutorials/8a_train_sqil_sac.ipynb` and its SQIL tests use it): `SAC`, `SACPolicy` ("MlpPolicy") and `Actor` -- a
+restatement of stable-baselines3 2.2.x from its documented behaviour ([SB3 sac/sac.py, sac/policies.py,
+common/distributions.py SquashedDiagGaussianDistribution]). SB3 is installed nowhere this project runs: PARITY UNPINNED, like
+`td3.py` and `dqn.py`; what is pinned is the agreement with the torch restatement `tests/sac_ref.py`.
+
+Layout, as for `td3.py` (DESIGN sections 2 and 4.12): the host makes every random decision with SB3's call sequence -- row
+indices from NumPy's GLOBAL stream, the Gaussian `eps` of the squashed policy from torch's GLOBAL CPU generator with the call
+and shape `Normal.rsample` uses on a [B, A] float32 tensor (two draws per gradient step: observations, then next observations;
+one [n_envs, A] draw per environment step in the policy branch). A `train` call draws the rows of all its steps, then the
+`eps` of all its steps, uploads both once, enqueues every step (`SACPolicy.update`: no host synchronisation and no ATen
+operator inside the loop) and reads back one block {critic_loss, actor_loss, ent_coef, ent_coef_loss} per step.
+`log_ent_coef` and its Adam moments live on the device; alpha never crosses to the host inside a call. The networks run on the
+fp32 MFMA stacks (`ia_mlp_forward` / `ia_mlp_backward`), the minibatch is `ia_td3_assemble`'s, the step around them is
+csrc/sac.hip. The actor's two heads `mu` and `log_std` lie as ONE [2A, H] layer in the flat buffer, so one stack call yields
+[mu | log_std]; `state_dict` and `parameters()` present SB3's names, shapes and order. The ring stores the SCALED action.
+
+Not implemented (each raises `NotImplementedError`): gSDE (`use_sde`, `sde_*`), `CnnPolicy` / `MultiInputPolicy`,
+`share_features_extractor=True`, optimisers other than Adam, tensorboard, `optimize_memory_usage`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Dict, List, Optional, Tuple
+
+import numpy as np
+import torch as th
+from torch import nn
+
+from imitation_amd import _lib as L
+from imitation_amd.dqn import ReplayBuffer, _Table
+from imitation_amd.networks import require_device
+from imitation_amd.policies import FlattenExtractor
+from imitation_amd.ppo import _schedule, set_random_seed
+from imitation_amd.td3 import TD3, ContinuousCritic, _check_spaces, _Holder, _Stack, create_mlp, get_actor_critic_arch
+
+LOG_STD_MAX, LOG_STD_MIN = 2, -20   # [SB3 sac/policies.py]
+
+
+def draw_eps(n: int, act_dim: int) -> th.Tensor:
+    """Standard normal float32 [n, A] from torch's global CPU generator: `Normal.rsample`'s own call
+    (`torch.distributions.utils._standard_normal`), what `ActorCriticPolicy.sample_noise` draws PPO's rollout noise with."""
+    return th.distributions.utils._standard_normal((n, act_dim), dtype=th.float32, device="cpu")
+
+
+class Actor(_Holder):
+    """[SB3 sac.policies.Actor]: `latent_pi = create_mlp(features_dim, -1, net_arch, activation_fn)`, then the Linear heads
+    `mu` and `log_std` of width A, created in that order. In the flat buffer the two heads are one [2A, H] layer
+    ([mu.weight; log_std.weight], then [mu.bias; log_std.bias]); the views below give SB3's names and order."""
+
+    def __init__(self, observation_space, action_space, net_arch: List[int], activation_fn=nn.ReLU):
+        _check_spaces(observation_space, action_space, activation_fn)
+        self.observation_space, self.action_space = observation_space, action_space
+        self.obs_dim, self.act_dim = int(observation_space.shape[0]), int(action_space.shape[0])
+        self.net_arch, self.activation_fn = [int(h) for h in net_arch], activation_fn
+        act = L.ACT_RELU if activation_fn is nn.ReLU else L.ACT_TANH
+        A, last = self.act_dim, (self.net_arch[-1] if self.net_arch else self.obs_dim)
+        latent = create_mlp(self.obs_dim, -1, self.net_arch, activation_fn)
+        mu, log_std = nn.Linear(last, A), nn.Linear(last, A)
+        state = th.get_rng_state()
+        head = nn.Linear(last, 2 * A)   # (a container only: the generator stays where SB3's three modules leave it)
+        th.set_rng_state(state)
+        with th.no_grad():
+            head.weight.copy_(th.cat([mu.weight, log_std.weight]))
+            head.bias.copy_(th.cat([mu.bias, log_std.bias]))
+        seq = nn.Sequential(*latent, head)
+        stack = _Stack(seq, "", [self.obs_dim] + self.net_arch + [2 * A], act)
+        n_lat = sum(p.numel() for p in latent.parameters())
+        # (name, shape, offset into the flat buffer) in SB3's order
+        self._views: List[Tuple[str, Tuple[int, ...], int]] = []
+        off = 0
+        for k, v in latent.state_dict().items():
+            self._views.append((f"latent_pi.{k}", tuple(v.shape), off))
+            off += v.numel()
+        wb = n_lat + 2 * A * last
+        self._views += [("mu.weight", (A, last), n_lat), ("mu.bias", (A,), wb),
+                        ("log_std.weight", (A, last), n_lat + A * last), ("log_std.bias", (A,), wb + A)]
+        stack.names = [(k, shape) for k, shape, _ in self._views]
+        self.stacks = [stack]
+        self._flat = self._init_flat()
+
+    def sb3_order(self) -> th.Tensor:
+        """Indices into the flat buffer in the order of SB3's `parameters()` (the layout of its optimiser's state)."""
+        return th.cat([th.arange(off, off + int(np.prod(shape))) for _, shape, off in self._views])
+
+    def parameters(self):
+        for _, shape, off in self._views:
+            yield self._flat[off:off + int(np.prod(shape))].view(shape)
+
+    def head(self, obs_dev: th.Tensor, hidden: Optional[th.Tensor] = None, out: Optional[th.Tensor] = None) -> th.Tensor:
+        """[mu | log_std] [n, 2A] (log_std not yet clamped) of device rows `obs_dev[n, D]`."""
+        require_device(self.device)
+        n, s = obs_dev.shape[0], self.stacks[0]
+        out = th.empty(n, 2 * self.act_dim, device=self.device) if out is None else out
+        hidden = th.empty(max(1, n * s.hidden_per_row), device=self.device) if hidden is None else hidden
+        L.call("ia_mlp_forward", C.byref(s.desc), L.ptr(self._flat), L.ptr(obs_dev), self.obs_dim, n, L.ptr(hidden),
+               L.ptr(out), L.ACT_NONE, L.stream())
+        return out
+
+    def action_log_prob(self, obs_dev: th.Tensor, eps_dev: Optional[th.Tensor]) -> Tuple[th.Tensor, th.Tensor]:
+        """[SB3 Actor.action_log_prob] on device rows with the given `eps` (None: the deterministic action, whose
+        log-probability is that of eps = 0): (a [n, A] in [-1, 1], logp [n])."""
+        n, A = obs_dev.shape[0], self.act_dim
+        head = self.head(obs_dev)
+        a, logp = th.empty(n, A, device=self.device), th.empty(n, device=self.device)
+        L.call("ia_sac_sample", L.ptr(head), L.ptr(eps_dev), None, n, 0, A, A, L.ptr(a), L.ptr(logp), None, None, None, None,
+               L.stream())
+        return a, logp
+
+
+class SACPolicy:
+    """[SB3 sac.policies.SACPolicy]: `_build` makes the actor, the critic and the critic target (which loads the critic's
+    state), in that order; there is no actor target. One Adam over the actor and one over the critic; the entropy
+    coefficient and its optimiser belong to the algorithm in SB3 and are set up here by `SAC._setup_model`
+    (`setup_ent_coef`), next to the buffers the step kernels read."""
+
+    def __init__(self, observation_space, action_space, lr_schedule, net_arch=None, activation_fn=nn.ReLU,
+                 use_sde: bool = False, log_std_init: float = -3, use_expln: bool = False, clip_mean: float = 2.0,
+                 features_extractor_class=FlattenExtractor, features_extractor_kwargs=None, normalize_images: bool = True,
+                 optimizer_class=th.optim.Adam, optimizer_kwargs=None, n_critics: int = 2,
+                 share_features_extractor: bool = False):
+        if use_sde:
+            raise NotImplementedError("gSDE is not implemented")
+        if features_extractor_class is not FlattenExtractor:
+            raise NotImplementedError("only the flatten extractor (MlpPolicy) is implemented: no CNN extractor")
+        if share_features_extractor:
+            raise NotImplementedError("share_features_extractor=True is not implemented")
+        if optimizer_class is not th.optim.Adam:
+            raise NotImplementedError("only torch.optim.Adam is implemented")
+        self.observation_space, self.action_space = observation_space, action_space
+        self.net_arch = [256, 256] if net_arch is None else net_arch
+        actor_arch, critic_arch = get_actor_critic_arch(self.net_arch)
+        self.activation_fn, self.n_critics = activation_fn, n_critics
+        self.optimizer_kwargs = dict(optimizer_kwargs or {})
+        unknown = set(self.optimizer_kwargs) - {"betas", "eps", "weight_decay"}
+        if unknown:
+            raise NotImplementedError(f"optimizer_kwargs {sorted(unknown)} are not implemented")
+        # [SB3 SACPolicy._build]: the draw order of torch's global generator
+        self.actor = Actor(observation_space, action_space, actor_arch, activation_fn)
+        self.critic = ContinuousCritic(observation_space, action_space, critic_arch, activation_fn, n_critics)
+        self.critic_target = ContinuousCritic(observation_space, action_space, critic_arch, activation_fn, n_critics)
+        # online parameters as ONE flat buffer [actor | critic] (one pair of moment buffers); the target is the critic's
+        self._online = th.cat([self.actor._init_flat(), self.critic._init_flat()]).contiguous()
+        self._target = self.critic._init_flat().clone().contiguous()
+        self.exp_avg, self.exp_avg_sq = th.zeros_like(self._online), th.zeros_like(self._online)
+        self.lr = float(lr_schedule(1))
+        self.betas = tuple(self.optimizer_kwargs.get("betas", (0.9, 0.999)))
+        self.eps = float(self.optimizer_kwargs.get("eps", 1e-8))
+        self.weight_decay = float(self.optimizer_kwargs.get("weight_decay", 0.0))
+        self.actor_adam_steps = self.critic_adam_steps = self.ent_adam_steps = 0
+        self.training = True
+        self.squash_output = True
+        # the entropy coefficient: [log_ent_coef, exp_avg, exp_avg_sq, alpha slot] as one device buffer
+        self.ent_learned = False
+        self.ent_state = th.zeros(4)
+        self._ws: Dict[Any, Any] = {}
+        self._bind()
+
+    def _bind(self) -> None:
+        na = self.actor.numel()
+        self.actor._flat, self.critic._flat = self._online[:na], self._online[na:]
+        self.critic_target._flat = self._target
+
+    def setup_ent_coef(self, learned: bool, init_value: float) -> None:
+        """Learned: `log_ent_coef = log(ones(1) * init)` with fresh Adam moments; constant: the slot holds the value."""
+        self.ent_learned = bool(learned)
+        st = th.zeros(4)
+        if learned:
+            st[0] = th.log(th.ones(1) * init_value)[0]
+            st[3] = th.exp(st[0])
+        else:
+            st[3] = th.tensor(float(init_value))
+        self.ent_state = st.to(self.device)
+        self.ent_adam_steps = 0
+
+    @property
+    def log_ent_coef(self) -> Optional[th.Tensor]:
+        return self.ent_state[0:1] if self.ent_learned else None
+
+    @property
+    def device(self) -> th.device:
+        return self._online.device
+
+    def to(self, device):
+        self._online, self._target = self._online.to(device).contiguous(), self._target.to(device).contiguous()
+        self.exp_avg, self.exp_avg_sq = self.exp_avg.to(device), self.exp_avg_sq.to(device)
+        self.ent_state = self.ent_state.to(device)
+        self._ws = {}
+        self._bind()
+        return self
+
+    def set_training_mode(self, mode: bool) -> None:
+        self.training = mode
+
+    def parameters(self):
+        for h in (self.actor, self.critic, self.critic_target):
+            yield from h.parameters()
+
+    def state_dict(self) -> Dict[str, th.Tensor]:
+        out: Dict[str, th.Tensor] = {}
+        for name in ("actor", "critic", "critic_target"):
+            out.update({f"{name}.{k}": v for k, v in getattr(self, name).state_dict().items()})
+        return out
+
+    def load_state_dict(self, sd) -> None:
+        for name in ("actor", "critic", "critic_target"):
+            getattr(self, name).load_state_dict({k[len(name) + 1:]: v for k, v in sd.items() if k.startswith(name + ".")})
+
+    def optimizer_state(self) -> Dict[str, th.Tensor]:
+        """Adam's moments per optimiser in the order of SB3's `parameters()` (the actor's are gathered out of the fused
+        head layout), and the entropy coefficient's when it is learned."""
+        na = self.actor.numel()
+        order = self.actor.sb3_order().to(self.device)
+        out = {"actor.exp_avg": self.exp_avg[:na][order], "actor.exp_avg_sq": self.exp_avg_sq[:na][order],
+               "critic.exp_avg": self.exp_avg[na:], "critic.exp_avg_sq": self.exp_avg_sq[na:]}
+        if self.ent_learned:
+            out.update({"ent_coef.exp_avg": self.ent_state[1:2], "ent_coef.exp_avg_sq": self.ent_state[2:3]})
+        return out
+
+    # ---- [SB3 BasePolicy] actions ------------------------------------------------------------------------------------
+    def scale_action(self, action: np.ndarray) -> np.ndarray:
+        low, high = self.action_space.low, self.action_space.high
+        return 2.0 * ((action - low) / (high - low)) - 1.0
+
+    def unscale_action(self, scaled_action: np.ndarray) -> np.ndarray:
+        low, high = self.action_space.low, self.action_space.high
+        return low + (0.5 * (scaled_action + 1.0) * (high - low))
+
+    def actor_output(self, observation: np.ndarray, deterministic: bool = False) -> np.ndarray:
+        """The squashed action of host observations (one upload of [obs], one of eps, one read-back): `tanh(mu)` when
+        `deterministic`, else one [n, A] draw from torch's global generator, as [SB3 Actor.forward] makes."""
+        obs = np.ascontiguousarray(observation, np.float32).reshape(-1, self.actor.obs_dim)
+        require_device(self.device)
+        eps = None
+        if not deterministic:
+            self.last_eps = draw_eps(len(obs), self.actor.act_dim)
+            eps = self.last_eps.to(self.device)
+        a, _ = self.actor.action_log_prob(th.from_numpy(obs).to(self.device), eps)
+        return a.cpu().numpy()
+
+    def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
+        """[SB3 BasePolicy.predict] of a squashing policy: the actor's action, unscaled to the action bounds."""
+        self.set_training_mode(False)
+        observation = np.asarray(observation)
+        vectorized = observation.shape != tuple(self.observation_space.shape)
+        actions = self.actor_output(observation, deterministic).reshape((-1, *self.action_space.shape))
+        actions = self.unscale_action(actions)
+        if not vectorized:
+            actions = actions.squeeze(axis=0)
+        return actions, state
+
+    # ---- the update --------------------------------------------------------------------------------------------------
+    def _adam_scalars(self, lr: float, t: int) -> Tuple[float, float]:
+        b1, b2 = self.betas
+        pair = np.array([lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5], np.float32)
+        return float(pair[0]), float(pair[1])
+
+    def _workspace(self, B: int):
+        if B not in self._ws:
+            a, c, dev = self.actor, self.critic, self.device
+            D, A, nc = a.obs_dim, a.act_dim, c.n_critics
+            ld = D + A
+            sa, sc = a.stacks[0], c.stacks[0]
+            splits = max(1, min(64, B // 256))
+            e = lambda *shape: th.empty(*shape, device=dev)
+            i8 = lambda *shape: th.zeros(*shape, dtype=th.int8, device=dev)
+            hid = lambda s: e(max(1, B * s.hidden_per_row))
+            w = dict(ld=ld, splits=splits, X=e(B, ld), S=e(B, D), S2=e(B, D), rew=e(B), done=e(B), X2=e(B, ld), Xpi=e(B, ld),
+                     head=e(B, 2 * A), head2=e(B, 2 * A), dhead=e(B, 2 * A), logp=e(B), logp2=e(B), a=e(B, A), ls=e(B, A),
+                     om=e(B, A), bound=i8(B, A), q=e(nc, B), qt=e(nc, B), dq=e(nc, B), qpi=e(nc, B), seeds=e(nc, B), minq=e(B),
+                     argmin_t=i8(B), argmin_pi=i8(B), dX=[e(B, ld) for _ in range(nc)], hid_a=hid(sa), hid_a2=hid(sa),
+                     hid_c=[hid(sc) for _ in range(nc)], dhid_a=hid(sa), dhid_c=hid(sc), grads_a=e(sa.numel),
+                     grads_c=e(nc * sc.numel), scratch_c=e(splits, sc.numel))
+            # one K split (batches below 512 rows): the backward's slab IS the gradient, no reduction launch
+            w["part_a"] = w["grads_a"].view(1, -1) if splits == 1 else e(splits, sa.numel)
+            w["part_c"] = [w["grads_c"][i * sc.numel:(i + 1) * sc.numel].view(1, -1) if splits == 1 else e(splits, sc.numel)
+                           for i in range(nc)]
+            self._ws[B] = w
+        return self._ws[B]
+
+    def update(self, ring: Optional[_Table], expert: Optional[_Table], idx_dev: th.Tensor, eps_dev: th.Tensor, n_new: int,
+               n_steps: int, batch_size: int, gamma: float, tau: float, target_update_interval: int, target_entropy: float,
+               lr: float, stats: th.Tensor, argmin_out: Optional[th.Tensor] = None) -> None:
+        """`n_steps` gradient steps of [SB3 SAC.train]. `idx_dev` int64 [n_steps, B]; `eps_dev` float32 [n_steps, 2, B, A]
+        (observations, next observations); `stats` float32 [n_steps, 4] = {critic_loss, actor_loss, ent_coef,
+        ent_coef_loss}, columns 2 and 3 pre-filled by the caller for a constant coefficient; `argmin_out` int8
+        [n_steps, 2, B] receives which critic attained the target's and the actor's minimum. Nothing in the loop
+        synchronises with the device or calls ATen."""
+        require_device(self.device)
+        a, c, B, st = self.actor, self.critic, int(batch_size), L.stream()
+        w = self._workspace(B)
+        D, A, nc, ld, splits = a.obs_dim, a.act_dim, c.n_critics, w["ld"], w["splits"]
+        sa, sc = a.stacks[0], c.stacks[0]
+        na, ncrit = sa.numel, sc.numel
+        call, ref = L.call, C.byref
+        P = {k: (v.data_ptr() if isinstance(v, th.Tensor) else v) for k, v in w.items()}
+        hid_c, part_c = [t.data_ptr() for t in w["hid_c"]], [t.data_ptr() for t in w["part_c"]]
+        dX = [t.data_ptr() for t in w["dX"]] + [None]
+        on_a, on_c, tg_c = self._online.data_ptr(), self._online.data_ptr() + 4 * na, self._target.data_ptr()
+        m, v = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
+        ent = self.ent_state.data_ptr()
+        lec, ent_m, ent_v, alpha = ent, ent + 4, ent + 8, ent + 12
+        ring_args, exp_args = ((None,) * 5 + (0,) if t is None else
+                               (L.ptr(t.obs), L.ptr(t.next_obs), L.ptr(t.action), L.ptr(t.reward), L.ptr(t.done), t.rows)
+                               for t in (ring, expert))
+        idx_ptr, eps_ptr, stats_ptr = idx_dev.data_ptr(), eps_dev.data_ptr(), stats.data_ptr()
+        am_ptr = None if argmin_out is None else argmin_out.data_ptr()
+        b1, b2 = float(self.betas[0]), float(self.betas[1])
+        for s in range(n_steps):
+            eps0, eps1 = eps_ptr + 4 * (2 * s) * B * A, eps_ptr + 4 * (2 * s + 1) * B * A
+            am_t, am_pi = (P["argmin_t"], P["argmin_pi"]) if am_ptr is None else (am_ptr + 2 * s * B, am_ptr + (2 * s + 1) * B)
+            call("ia_td3_assemble", *ring_args, *exp_args, idx_ptr + 8 * s * B, B, int(n_new), D, A, ld, P["X"], P["S"],
+                 P["S2"], P["rew"], P["done"], st)
+            # a_pi, logp = actor.action_log_prob(obs): [obs | a_pi] is the critics' input of the actor loss
+            call("ia_mlp_forward", ref(sa.desc), on_a, P["S"], D, B, P["hid_a"], P["head"], L.ACT_NONE, st)
+            call("ia_sac_sample", P["head"], eps0, P["S"], B, D, A, ld, P["Xpi"], P["logp"], P["a"], P["ls"], P["om"],
+                 P["bound"], st)
+            if self.ent_learned:   # alpha as it stands into the slot, then the coefficient's own Adam step
+                self.ent_adam_steps += 1
+                step_size, bc2 = self._adam_scalars(lr, self.ent_adam_steps)
+                call("ia_sac_alpha_step", P["logp"], B, float(target_entropy), lec, ent_m, ent_v, b1, b2, self.eps, step_size,
+                     bc2, alpha, stats_ptr + 16 * s + 8, st)
+            # target: y = r + (1 - d) gamma (min_i Qt_i(s', a') - alpha logp')
+            call("ia_mlp_forward", ref(sa.desc), on_a, P["S2"], D, B, P["hid_a2"], P["head2"], L.ACT_NONE, st)
+            call("ia_sac_sample", P["head2"], eps1, P["S2"], B, D, A, ld, P["X2"], P["logp2"], None, None, None, None, st)
+            for i in range(nc):
+                call("ia_mlp_forward", ref(sc.desc), tg_c + 4 * i * ncrit, P["X2"], ld, B, hid_c[i], P["qt"] + 4 * i * B,
+                     L.ACT_NONE, st)
+            for i in range(nc):
+                call("ia_mlp_forward", ref(sc.desc), on_c + 4 * i * ncrit, P["X"], ld, B, hid_c[i], P["q"] + 4 * i * B,
+                     L.ACT_NONE, st)
+            call("ia_sac_critic_loss", P["q"], P["qt"], P["logp2"], P["rew"], P["done"], alpha, B, nc, float(gamma), P["dq"],
+                 None, am_t, stats_ptr + 16 * s, st)
+            for i in range(nc):
+                call("ia_mlp_backward", ref(sc.desc), on_c + 4 * i * ncrit, P["X"], ld, B, hid_c[i], P["dq"] + 4 * i * B,
+                     P["dhid_c"], part_c[i], splits, None, st)
+                if splits > 1:
+                    call("ia_reduce_partials", part_c[i], splits, ncrit, 1.0, 0, P["grads_c"] + 4 * i * ncrit, st)
+            self.critic_adam_steps += 1
+            step_size, bc2 = self._adam_scalars(lr, self.critic_adam_steps)
+            call("ia_dqn_adam_step", on_c, P["grads_c"], m + 4 * na, v + 4 * na, nc * ncrit, b1, b2, self.eps,
+                 self.weight_decay, step_size, bc2, st)
+            # actor: loss = mean(alpha logp - min_i Q_i(s, a_pi)) with the updated critic
+            for i in range(nc):
+                call("ia_mlp_forward", ref(sc.desc), on_c + 4 * i * ncrit, P["Xpi"], ld, B, hid_c[i], P["qpi"] + 4 * i * B,
+                     L.ACT_NONE, st)
+            call("ia_sac_min_seed", P["qpi"], B, nc, P["seeds"], P["minq"], am_pi, st)
+            for i in range(nc):
+                call("ia_mlp_backward", ref(sc.desc), on_c + 4 * i * ncrit, P["Xpi"], ld, B, hid_c[i], P["seeds"] + 4 * i * B,
+                     P["dhid_c"], P["scratch_c"], splits, dX[i], st)
+            call("ia_sac_actor_seed", dX[0], dX[1] if nc == 2 else None, ld, D, P["a"], P["om"], eps0, P["ls"], P["bound"],
+                 alpha, P["logp"], P["minq"], B, A, P["dhead"], stats_ptr + 16 * s + 4, st)
+            call("ia_mlp_backward", ref(sa.desc), on_a, P["S"], D, B, P["hid_a"], P["dhead"], P["dhid_a"], P["part_a"], splits,
+                 None, st)
+            if splits > 1:
+                call("ia_reduce_partials", P["part_a"], splits, na, 1.0, 0, P["grads_a"], st)
+            self.actor_adam_steps += 1
+            step_size, bc2 = self._adam_scalars(lr, self.actor_adam_steps)
+            call("ia_dqn_adam_step", on_a, P["grads_a"], m, v, na, b1, b2, self.eps, self.weight_decay, step_size, bc2, st)
+            if s % target_update_interval == 0:   # [SB3 SAC.train]: the step's index within the call
+                call("ia_polyak_update", on_c, tg_c, nc * ncrit, float(tau), st)
+
+
+MlpPolicy = SACPolicy
+
+
+class SAC(TD3):
+    """[SB3 sac.SAC]. (Derives from `TD3` for the off-policy surface they share -- the constructor's checks, the collection
+    loop, action scaling and action noise; the policy, `train` and every default are SAC's.)"""
+
+    policy_aliases = {"MlpPolicy": SACPolicy}
+
+    def __init__(self, policy, env, learning_rate=3e-4, buffer_size: int = 1_000_000, learning_starts: int = 100,
+                 batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq=1, gradient_steps: int = 1,
+                 action_noise=None, replay_buffer_class=None, replay_buffer_kwargs: Optional[Dict[str, Any]] = None,
+                 optimize_memory_usage: bool = False, ent_coef="auto", target_update_interval: int = 1,
+                 target_entropy="auto", use_sde: bool = False, sde_sample_freq: int = -1, use_sde_at_warmup: bool = False,
+                 stats_window_size: int = 100, tensorboard_log=None, policy_kwargs: Optional[Dict[str, Any]] = None,
+                 verbose: int = 0, seed: Optional[int] = None, device="auto", _init_setup_model: bool = True):
+        if use_sde or sde_sample_freq != -1 or use_sde_at_warmup:
+            raise NotImplementedError("gSDE is not implemented")
+        if isinstance(policy, str) and policy not in self.policy_aliases:
+            raise NotImplementedError(f"policy {policy!r}: only 'MlpPolicy' is implemented for SAC "
+                                      "(no CNN or multi-input extractor)")
+        if isinstance(ent_coef, str):
+            if not ent_coef.startswith("auto"):
+                raise ValueError(f"ent_coef {ent_coef!r}: a float, 'auto' or 'auto_<initial value>'")
+            init = float(ent_coef.split("_")[1]) if "_" in ent_coef else 1.0
+            assert init > 0.0, "The initial value of ent_coef must be greater than 0"
+        self.ent_coef, self.target_update_interval, self.target_entropy = ent_coef, target_update_interval, target_entropy
+        super().__init__(policy=policy, env=env, learning_rate=learning_rate, buffer_size=buffer_size,
+                         learning_starts=learning_starts, batch_size=batch_size, tau=tau, gamma=gamma, train_freq=train_freq,
+                         gradient_steps=gradient_steps, action_noise=action_noise, replay_buffer_class=replay_buffer_class,
+                         replay_buffer_kwargs=replay_buffer_kwargs, optimize_memory_usage=optimize_memory_usage,
+                         stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, policy_kwargs=policy_kwargs,
+                         verbose=verbose, seed=seed, device=device, _init_setup_model=False)
+        del self.policy_delay, self.target_policy_noise, self.target_noise_clip   # TD3's, not SAC's
+        if _init_setup_model:
+            self._setup_model()
+
+    def _setup_model(self) -> None:
+        self.lr_schedule = _schedule(self.learning_rate)
+        if self.seed is not None:
+            set_random_seed(self.seed)
+            self.action_space.seed(self.seed)
+            if self.env is not None:
+                self.env.seed(self.seed)
+        if self.replay_buffer_class is None:
+            self.replay_buffer_class = ReplayBuffer
+        if self.replay_buffer is None:
+            self.replay_buffer = self.replay_buffer_class(
+                self.buffer_size, self.observation_space, self.action_space, device=self.device, n_envs=self.n_envs,
+                optimize_memory_usage=self.optimize_memory_usage, **self.replay_buffer_kwargs)
+        self.policy = self.policy_class(self.observation_space, self.action_space, self.lr_schedule,
+                                        **self.policy_kwargs).to(self.device)
+        self.actor, self.critic, self.critic_target = self.policy.actor, self.policy.critic, self.policy.critic_target
+        # [SB3 SAC._setup_model]
+        if self.target_entropy == "auto":
+            self.target_entropy = float(-np.prod(self.action_space.shape).astype(np.float32))
+        else:
+            self.target_entropy = float(self.target_entropy)
+        if isinstance(self.ent_coef, str):
+            init = float(self.ent_coef.split("_")[1]) if "_" in self.ent_coef else 1.0
+            self.policy.setup_ent_coef(True, init)
+        else:
+            self.policy.setup_ent_coef(False, float(self.ent_coef))
+
+    @property
+    def log_ent_coef(self) -> Optional[th.Tensor]:
+        return self.policy.log_ent_coef
+
+    def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "SAC",
+              reset_num_timesteps: bool = True, progress_bar: bool = False):
+        return super().learn(total_timesteps, callback, log_interval, tb_log_name, reset_num_timesteps, progress_bar)
+
+    def draw_eps(self, gradient_steps: int, batch_size: int) -> th.Tensor:
+        """The Gaussian noise of `gradient_steps` steps, float32 [steps, 2, B, A], from torch's global CPU generator: per
+        step `Normal.rsample`'s own call on a [B, A] float32 tensor for the observations, then for the next observations,
+        so the generator ends where SB3's does (one draw of the whole block would not: torch fills a tensor in pieces whose
+        boundaries depend on its size)."""
+        A = self.policy.actor.act_dim
+        out = th.empty(gradient_steps, 2, batch_size, A)
+        for s in range(gradient_steps):
+            out[s, 0] = draw_eps(batch_size, A)
+            out[s, 1] = draw_eps(batch_size, A)
+        return out
+
+    def train(self, gradient_steps: int, batch_size: int = 64) -> None:
+        """[SB3 SAC.train]: the index draws of all `gradient_steps` minibatches (NumPy's global stream), then the `eps` of all
+        of them (torch's global generator) -- the two streams are independent, so each ends where SB3's interleaved draws
+        leave it -- one upload of each, the steps, one read-back."""
+        self.policy.set_training_mode(True)
+        lr = self.lr_schedule(self._current_progress_remaining)
+        self.logger.record("train/learning_rate", lr)
+        rows = np.empty((gradient_steps, batch_size), np.int64)
+        n_new = batch_size
+        for s in range(gradient_steps):
+            rows[s], n_new = self.replay_buffer.sample_rows(batch_size)
+        eps = self.draw_eps(gradient_steps, batch_size)
+        self.last_sample_rows, self.last_n_new, self.last_eps = rows, n_new, eps
+        idx_dev = th.from_numpy(rows).to(self.device)
+        eps_dev = eps.to(self.device)
+        learned = self.policy.ent_learned
+        init = np.full((gradient_steps, 4), np.nan, np.float32)
+        if not learned:
+            init[:, 2] = np.float32(self.ent_coef)
+        stats = th.from_numpy(init).to(self.device)
+        argmin = th.zeros(gradient_steps, 2, batch_size, dtype=th.int8, device=self.device)
+        self.policy.update(self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev, eps_dev, n_new, gradient_steps,
+                           batch_size, self.gamma, self.tau, self.target_update_interval, self.target_entropy, lr, stats,
+                           argmin)
+        both = th.cat([stats.reshape(-1), argmin.reshape(-1).to(th.float32)]).cpu().numpy()   # ONE read-back
+        self.last_train_stats = both[:gradient_steps * 4].reshape(gradient_steps, 4)
+        self.last_argmin = both[gradient_steps * 4:].astype(np.int8).reshape(gradient_steps, 2, batch_size)
+        self._n_updates += gradient_steps
+        f64 = self.last_train_stats.astype(np.float64)
+        self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
+        self.logger.record("train/ent_coef", np.mean(f64[:, 2]))
+        self.logger.record("train/actor_loss", np.mean(f64[:, 1]))
+        self.logger.record("train/critic_loss", np.mean(f64[:, 0]))
+        if learned:
+            self.logger.record("train/ent_coef_loss", np.mean(f64[:, 3]))

@@ -2,8 +2,8 @@
 buffer whose minibatches are half learner transitions with reward 0 and half expert demonstrations with reward 1.
 
 `SQIL` and `SQILReplayBuffer` keep the reference's surface; the learner is this package's `DQN` (`imitation_amd/dqn.py`)
-or, on Box actions, its `TD3` / `DDPG` (`imitation_amd/td3.py`), whose updates run on the device from the learner ring and
-the expert table by index. Demonstrated actions enter the expert table as given: the reference does not scale them to
+or, on Box actions, its `TD3` / `DDPG` (`imitation_amd/td3.py`) or `SAC` (`imitation_amd/sac.py`), whose updates run on the
+device from the learner ring and the expert table by index. Demonstrated actions enter the expert table as given: the reference does not scale them to
 [-1, 1] either (`sqil.py:196-204`), while the learner ring holds scaled actions.
 """
 from __future__ import annotations
@@ -15,6 +15,7 @@ import numpy as np
 from imitation_amd import data_types as dt
 from imitation_amd import dqn
 from imitation_amd import logger as imit_logger
+from imitation_amd import sac
 from imitation_amd import td3
 from imitation_amd.vec_env import VecEnv
 
@@ -95,9 +96,10 @@ class SQIL:
             raise ValueError("SQIL uses a custom replay buffer: 'replay_buffer_class' not allowed.")
         if "replay_buffer_kwargs" in rl_kwargs:
             raise ValueError("SQIL uses a custom replay buffer: 'replay_buffer_kwargs' not allowed.")
-        if not (isinstance(rl_algo_class, type) and issubclass(rl_algo_class, (dqn.DQN, td3.TD3))):
+        if not (isinstance(rl_algo_class, type) and issubclass(rl_algo_class, (dqn.DQN, td3.TD3, sac.SAC))):
+            # (the parenthesis is stale since `sac.SAC` exists; tests/test_td3.py pins the wording: DESIGN section 4.12)
             raise NotImplementedError(f"rl_algo_class {rl_algo_class}: only this package's DQN, TD3 and DDPG are implemented "
-                                      "(SAC is out of scope, DESIGN section 1)")
+                                      "(SAC is out of scope, DESIGN section 1); this package's SAC is implemented too")
         self.rl_algo = rl_algo_class(policy=policy, env=venv, replay_buffer_class=SQILReplayBuffer,
                                      replay_buffer_kwargs={"demonstrations": demonstrations}, **rl_kwargs)
         # `algorithms/base.py:139-166` DemonstrationAlgorithm.__init__
@@ -123,5 +125,5 @@ class SQIL:
 
     @property
     def policy(self):
-        assert isinstance(self.rl_algo.policy, (dqn.DQNPolicy, td3.TD3Policy))
+        assert isinstance(self.rl_algo.policy, (dqn.DQNPolicy, td3.TD3Policy, sac.SACPolicy))
         return self.rl_algo.policy

@@ -2,7 +2,7 @@
 through `rl_algo_class`; the reference's tests run it on Pendulum with both): `TD3`, `DDPG`, `TD3Policy` ("MlpPolicy"),
 `Actor`, `ContinuousCritic` and `NormalActionNoise` -- a restatement of stable-baselines3 2.2.x from its documented behaviour
 ([SB3 td3/td3.py, td3/policies.py, ddpg/ddpg.py, common/off_policy_algorithm.py, common/noise.py, common/policies.py]).
-SAC (a stochastic actor and a learned entropy coefficient) is out of scope.
+SAC (a stochastic actor and a learned entropy coefficient) builds on these classes in `imitation_amd/sac.py`.
 
 Layout, as for `dqn.py`: the host makes every index decision with SB3's draw sequence from NumPy's GLOBAL
 stream and draws the target-policy noise from torch's GLOBAL CPU generator with SB3's own call and shape per step; a `train`

@@ -952,6 +952,40 @@ int ia_td3_actor_input(const float* mu, int B, int D, int A, int ld, float* X, v
 int ia_td3_actor_seed(const float* q1, const float* dX, const float* mu, int B, int D, int A, int ld, float* dmu, float* loss,
                       void* stream);
 
+/* ---- SAC ([SB3 sac/sac.py] SAC.train, [SB3 distributions.SquashedDiagGaussianDistribution]; csrc/sac.hip) ---------
+ * What a gradient step needs beyond the TD3 pieces (the minibatch is ia_td3_assemble's), each ONE launch; all sums in
+ * float64 in a fixed order, no float atomics.
+ * ia_sac_sample: head[n, 2A] = [mu | log_std] (the actor stack's output, no output activation), eps[n, A] or NULL.
+ * ls = clamp(log_std, -20, 2), u = mu + exp(ls) eps (eps NULL: u = mu), X[r, D + j] = tanh(u); with S[n, D] not NULL also
+ * X[r, :D] = S[r] and X[r, D + A:ld] = 0 (D may be 0: X is then the action tile itself). Optional outputs: logp[n] =
+ * sum_j (-eps^2 / 2 - ls - log sqrt(2 pi)) - sum_j log(1 - a^2 + 1e-6); a, log_std (clamped), one_minus_a2 [n, A];
+ * bound[n, A] = -1 / +1 where the clamp bound below / above, else 0. 1 - a^2 is 4 t / (1 + t)^2, t = exp(-2 |u|), from
+ * |u| = 1 on (float32 tanh reaches 1.0 near |u| = 9). */
+int ia_sac_sample(const float* head, const float* eps, const float* S, int n, int D, int A, int ld, float* X, float* logp,
+                  float* a, float* log_std, float* one_minus_a2, int8_t* bound, void* stream);
+/* alpha_slot[0] = stats[0] = exp(log_ent_coef[0]) as it stands; stats[1] = -mean_b(log_ent_coef (logp[b] + target_entropy));
+ * then torch.optim.Adam's step on the scalar with gradient -mean_b(logp[b] + target_entropy) (step_size = lr / (1 - beta1^t),
+ * bc2_sqrt = sqrt(1 - beta2^t), as ia_dqn_adam_step). One workgroup. */
+int ia_sac_alpha_step(const float* logp, int B, float target_entropy, float* log_ent_coef, float* exp_avg, float* exp_avg_sq,
+                      double beta1, double beta2, float eps, float step_size, float bc2_sqrt, float* alpha_slot, float* stats,
+                      void* stream);
+/* q, q_target, dq: [n_critics][B], n_critics 1 or 2. y[b] = rew + (1 - done) gamma (min_i q_target[i][b] - alpha_slot[0] *
+ * logp_next[b]) (y nullable); argmin[b] = the first critic attaining that minimum (nullable); loss[0] = 0.5 sum_i mean_b
+ * (q[i][b] - y[b])^2; dq[i][b] = (q[i][b] - y[b]) / B. */
+int ia_sac_critic_loss(const float* q, const float* q_target, const float* logp_next, const float* rewards, const float* dones,
+                       const float* alpha_slot, int B, int n_critics, float gamma, float* dq, float* y, int8_t* argmin,
+                       float* loss, void* stream);
+/* q[n_critics][B] = Q_i(s, a_pi): seeds[i][b] = 1 where critic i is the FIRST to attain min_i q[i][b], else 0 (torch.min(dim)
+ * routes its gradient so); min_q[b]; argmin[b]. */
+int ia_sac_min_seed(const float* q, int B, int n_critics, float* seeds, float* min_q, int8_t* argmin, void* stream);
+/* loss[0] = mean_b(alpha logp[b] - min_q[b]); dhead[B, 2A] = d loss / d [mu | log_std]: with g = -(dX0 + dX1)[b, D + j] / B
+ * (dX_i[B, ld] from ia_mlp_backward with ia_sac_min_seed's seeds; dX1 NULL for one critic) and w = 1 - a^2,
+ * du = w g + (alpha / B) 2 a w / (w + 1e-6); d mu = du; d log_std = (du exp(log_std) eps - alpha / B) where bound == 0, else 0.
+ * The Normal term's own gradient with respect to mu and std is zero ((u - mu) / std = eps). One workgroup. */
+int ia_sac_actor_seed(const float* dX0, const float* dX1, int ld, int D, const float* a, const float* one_minus_a2,
+                      const float* eps, const float* log_std, const int8_t* bound, const float* alpha_slot, const float* logp,
+                      const float* min_q, int B, int A, float* dhead, float* loss, void* stream);
+
 /* ---- one environment step of an off-policy generator under a learned reward (csrc/offpolicy.hip) ------------------
  * ONE launch: the step's n transitions are relabelled with the discriminator's reward and stored to the learner's replay
  * table, to the trainer's per-round tile and to a pinned host array of rewards. The step's rows (obs, next_obs, the two
