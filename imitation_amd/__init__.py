@@ -31,6 +31,8 @@ from imitation_amd.dqn import DQN, DQNPolicy, QNetwork  # noqa: F401
 from imitation_amd.sqil import SQIL, SQILReplayBuffer  # noqa: F401
 from imitation_amd.td3 import DDPG, TD3, Actor, ContinuousCritic, NormalActionNoise, TD3Policy  # noqa: F401
 from imitation_amd.sac import SAC, SACPolicy  # noqa: F401
+from imitation_amd import replay_buffer_wrapper  # noqa: F401
+from imitation_amd.replay_buffer_wrapper import ReplayBufferRewardWrapper  # noqa: F401
 
 
 def configure_logger(folder=None, format_strs=None):

@@ -107,6 +107,17 @@ class OffpolicyStepArgs(C.Structure):
                 [("tile_row", C.c_int64), ("tile_rows", C.c_int64), ("rewards_host", C.c_void_p)])
 
 
+class ReplayRelabelArgs(C.Structure):
+    """Mirror of `ia_replay_relabel_args` (include/imitation_hip.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("obs", "next_obs", "act_f32", "act_i64", "done")] + [("ring_rows", C.c_int64)] +
+                [("idx", C.c_void_p), ("n", C.c_int64)] +
+                [(n, C.c_int) for n in ("obs_dim", "act_dim", "use_state", "use_action", "use_next_state", "use_done")] +
+                [("desc", C.POINTER(MlpDesc)), ("params", C.c_void_p)] +
+                [("norm_mean", C.c_void_p), ("norm_var", C.c_void_p), ("norm_eps", C.c_float)] +
+                [("out_mean", C.c_void_p), ("out_var", C.c_void_p), ("out_eps", C.c_float)] +
+                [("reward", C.c_void_p)])
+
+
 class HipExtensionMissing(RuntimeError):
     pass
 
@@ -291,6 +302,10 @@ _SIGS = {
     "ia_offpolicy_step_rows": ([], C.c_int),
     "ia_offpolicy_step_ok": ([C.POINTER(MlpDesc), _I, _I, _I, _I, _I, _I], C.c_int),
     "ia_offpolicy_step": ([C.POINTER(OffpolicyStepArgs), _P], C.c_int),
+    "ia_replay_relabel_ok": ([C.POINTER(MlpDesc), _I, _I, _I, _I, _I, _I], C.c_int),
+    "ia_replay_relabel": ([C.POINTER(ReplayRelabelArgs), _P], C.c_int),
+    "ia_replay_relabel_general_ws_doubles": ([C.POINTER(MlpDesc), _L], C.c_int64),
+    "ia_replay_relabel_general": ([C.POINTER(ReplayRelabelArgs), _D, _D, _P, _L, _P], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

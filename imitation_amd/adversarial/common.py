@@ -129,6 +129,11 @@ class AdversarialTrainer(abc.ABC):
         if isinstance(gen_algo, sac.SAC):
             raise NotImplementedError("a SAC generator is not implemented for the adversarial trainers yet: SAC runs under "
                                       "SQIL only (DESIGN section 4.12); use PPO, DQN, TD3 or DDPG as gen_algo")
+        from imitation_amd.replay_buffer_wrapper import ReplayBufferRewardWrapper
+        if isinstance(getattr(gen_algo, "replay_buffer", None), ReplayBufferRewardWrapper):
+            raise NotImplementedError("a generator whose replay_buffer is a ReplayBufferRewardWrapper is not implemented for "
+                                      "the adversarial trainers: the trainer's fused reward step owns the ring's reward "
+                                      "column (DESIGN section 4.13); give the generator a plain ReplayBuffer")
         self._device = th.device(gen_algo.device)
         require_device(self._device)
         L.load()  # fail loudly here if the HIP extension is missing

@@ -711,6 +711,20 @@ class OffPolicyAlgorithm:
     def _on_step(self) -> None:
         pass
 
+    def _run_updates(self, rows: np.ndarray, idx_dev: th.Tensor, run) -> None:
+        """The gradient steps of one `train` call, `run(lo, hi)` being steps [lo, hi) of it, behind the sample-time reward
+        relabelling of a `ReplayBufferRewardWrapper` (imitation_amd/replay_buffer_wrapper.py): every sampled row of the
+        call relabelled on the device, then one `run` over all steps; or, for a `reward_fn` only the host can call, per
+        step its rows relabelled and that one step run. Any other buffer: `run(0, G)` as it stands."""
+        G = len(rows)
+        relabel = getattr(self.replay_buffer, "relabel_for_train", None)
+        if relabel is None or relabel(idx_dev):
+            run(0, G)
+            return
+        for s in range(G):
+            self.replay_buffer.relabel_step(rows[s], idx_dev[s])
+            run(s, s + 1)
+
     def _on_episode_end(self, env_index: int, n_envs: int) -> None:
         """[SB3 collect_rollouts]: where an episode's end resets the action noise."""
 
@@ -908,8 +922,9 @@ class DQN(OffPolicyAlgorithm):
         self.last_sample_rows, self.last_n_new = rows, n_new
         idx_dev = th.from_numpy(rows).to(self.device)
         stats = th.empty(gradient_steps, 2, device=self.device)
-        self.policy.update(self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev, n_new, gradient_steps,
-                           batch_size, self.gamma, self.max_grad_norm, lr, stats)
+        self._run_updates(rows, idx_dev, lambda lo, hi: self.policy.update(
+            self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev[lo:hi], n_new, hi - lo, batch_size,
+            self.gamma, self.max_grad_norm, lr, stats[lo:hi]))
         self.last_train_stats = stats.cpu().numpy()
         self._n_updates += gradient_steps
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")

@@ -280,7 +280,7 @@ class SACPolicy:
 
     def update(self, ring: Optional[_Table], expert: Optional[_Table], idx_dev: th.Tensor, eps_dev: th.Tensor, n_new: int,
                n_steps: int, batch_size: int, gamma: float, tau: float, target_update_interval: int, target_entropy: float,
-               lr: float, stats: th.Tensor, argmin_out: Optional[th.Tensor] = None) -> None:
+               lr: float, stats: th.Tensor, argmin_out: Optional[th.Tensor] = None, step0: int = 0) -> None:
         """`n_steps` gradient steps of [SB3 SAC.train]. `idx_dev` int64 [n_steps, B]; `eps_dev` float32 [n_steps, 2, B, A]
         (observations, next observations); `stats` float32 [n_steps, 4] = {critic_loss, actor_loss, ent_coef,
         ent_coef_loss}, columns 2 and 3 pre-filled by the caller for a constant coefficient; `argmin_out` int8
@@ -357,7 +357,8 @@ class SACPolicy:
             self.actor_adam_steps += 1
             step_size, bc2 = self._adam_scalars(lr, self.actor_adam_steps)
             call("ia_dqn_adam_step", on_a, P["grads_a"], m, v, na, b1, b2, self.eps, self.weight_decay, step_size, bc2, st)
-            if s % target_update_interval == 0:   # [SB3 SAC.train]: the step's index within the call
+            # [SB3 SAC.train]: the step's index within the call (`step0`: this call's first step within a `train` call split)
+            if (step0 + s) % target_update_interval == 0:
                 call("ia_polyak_update", on_c, tg_c, nc * ncrit, float(tau), st)
 
 
@@ -466,9 +467,10 @@ class SAC(TD3):
             init[:, 2] = np.float32(self.ent_coef)
         stats = th.from_numpy(init).to(self.device)
         argmin = th.zeros(gradient_steps, 2, batch_size, dtype=th.int8, device=self.device)
-        self.policy.update(self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev, eps_dev, n_new, gradient_steps,
-                           batch_size, self.gamma, self.tau, self.target_update_interval, self.target_entropy, lr, stats,
-                           argmin)
+        self._run_updates(rows, idx_dev, lambda lo, hi: self.policy.update(
+            self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev[lo:hi], eps_dev[lo:hi], n_new, hi - lo,
+            batch_size, self.gamma, self.tau, self.target_update_interval, self.target_entropy, lr, stats[lo:hi],
+            argmin[lo:hi], step0=lo))
         both = th.cat([stats.reshape(-1), argmin.reshape(-1).to(th.float32)]).cpu().numpy()   # ONE read-back
         self.last_train_stats = both[:gradient_steps * 4].reshape(gradient_steps, 4)
         self.last_argmin = both[gradient_steps * 4:].astype(np.int8).reshape(gradient_steps, 2, batch_size)

@@ -544,9 +544,11 @@ class TD3(OffPolicyAlgorithm):
         idx_dev = th.from_numpy(rows).to(self.device)
         noise_dev = noise.to(self.device)
         stats = th.full((gradient_steps, 2), float("nan"), device=self.device)
-        self.last_actor_steps = self.policy.update(
-            self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev, noise_dev, n_new, gradient_steps, batch_size,
-            self.gamma, self.tau, self.policy_delay, self.target_noise_clip, self._n_updates, lr, stats)
+        self.last_actor_steps = []
+        self._run_updates(rows, idx_dev, lambda lo, hi: self.last_actor_steps.extend(self.policy.update(
+            self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev[lo:hi], noise_dev[lo:hi], n_new, hi - lo,
+            batch_size, self.gamma, self.tau, self.policy_delay, self.target_noise_clip, self._n_updates + lo, lr,
+            stats[lo:hi])))
         self.last_train_stats = stats.cpu().numpy()
         self._n_updates += gradient_steps
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")

@@ -1024,6 +1024,42 @@ int ia_offpolicy_step_ok(const ia_mlp_desc* d, int obs_dim, int act_dim, int use
                          int use_done);
 int ia_offpolicy_step(const ia_offpolicy_step_args* a, void* stream);
 
+/* ---- sample-time reward relabelling of a replay ring (csrc/relabel.hip) ------------------------------------------------
+ * ONE launch for n int64 ring indices (all the minibatches of a `train` call): reward[idx[i]] = the reward net's
+ * processed prediction of ring row idx[i]:
+ *   ring columns:     obs / next_obs float32 [ring_rows, obs_dim]; act_f32 float32 [ring_rows, act_dim] or act_i64 int64
+ *                     [ring_rows] (one-hot to act_dim columns), exactly one of them; done float32 [ring_rows];
+ *   input:            [state | action | next_state | done] by the use_* flags, normalised as (x - mean) / sqrt(var + eps)
+ *                     when norm_mean / norm_var [D] are given;
+ *   stack:            desc = D -> H1 -> H2 -> 1 with D <= 64, H1 and H2 in {32, 64}, ReLU or Tanh (the predicate below;
+ *                     any other IA_ERR_UNSUPPORTED), params in torch's order (weight [out, in], bias, per layer);
+ *   output:           (r - out_mean[0]) / sqrt(out_var[0] + out_eps) when out_mean / out_var (device scalars) are given;
+ *   reward:           float32 [ring_rows]; only the rows idx names are written (duplicates write equal values); an index
+ *                     outside [0, ring_rows) is skipped.
+ * No read passes the last element of a ring column or idx[n - 1]. A row's reward depends on neither the other rows nor n;
+ * every sum has a fixed order; no atomics. */
+typedef struct {
+  const float* obs; const float* next_obs; const float* act_f32; const int64_t* act_i64; const float* done;
+  int64_t ring_rows;
+  const int64_t* idx; int64_t n;
+  int obs_dim, act_dim, use_state, use_action, use_next_state, use_done;
+  const ia_mlp_desc* desc; const float* params;
+  const float* norm_mean; const float* norm_var; float norm_eps;
+  const float* out_mean; const float* out_var; float out_eps;
+  float* reward;
+} ia_replay_relabel_args;
+int ia_replay_relabel_ok(const ia_mlp_desc* d, int obs_dim, int act_dim, int use_state, int use_action, int use_next_state,
+                         int use_done);
+int ia_replay_relabel(const ia_replay_relabel_args* a, void* stream);
+/* The same relabelling for ANY stack D -> h1 -> ... -> 1 (up to IA_MAX_LAYERS layers, no / ReLU / Tanh hidden activation), ONE
+ * launch, one thread per row with the whole forward in float64 (inputs, both norms, accumulators, activations): the stored
+ * float32 reward is the rounding of the float64 forward, whatever n. `norm_eps` / `out_eps` replace the record's float fields;
+ * `ws` holds at least ia_replay_relabel_general_ws_doubles(desc, n) doubles (IA_ERR_ARG otherwise; it does not grow with n
+ * beyond 8192 rows). The fall-back of shapes ia_replay_relabel_ok refuses. */
+int64_t ia_replay_relabel_general_ws_doubles(const ia_mlp_desc* d, int64_t n);
+int ia_replay_relabel_general(const ia_replay_relabel_args* a, double norm_eps, double out_eps, double* ws, int64_t ws_doubles,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
