@@ -255,6 +255,7 @@ _SIGS = {
     "ia_ppo_update_xcd_pack": ([_I], C.c_int),
     "ia_ppo_update_assume_cus": ([_I], C.c_int),
     "ia_ppo_update_tower_split": ([_I], C.c_int),
+    "ia_ppo_update_slice_owner": ([_I], C.c_int),
     "ia_ppo_update": ([C.POINTER(PolicyDesc), _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F,
                        _F, _F, _F, _P, _P, _D, _D, _D, _F, _L, _P, _P, _P], C.c_int),
     "ia_ppo_update_sharded_ws_floats": ([C.POINTER(PolicyDesc), _I, _I], C.c_int64),

@@ -4667,7 +4667,15 @@ __global__ __launch_bounds__(64 * NW) void ppo_epoch_ll2_kernel(
 // result. The parity argument holds with 2 nblk owners: a word of step s + 2 is written only after every owner has
 // published its slice of step s + 1 (hop 2 polls the WHOLE sum vector), hence has read all slabs of step s + 1 -- and a
 // workgroup writes its slab of step s + 1 only behind its own hop 2 of step s, so nobody still reads the buffer.
-template <int NPT, bool TIMING, int KS1, bool LOCAL, bool SHARD, bool SMALL, bool TSPLIT>
+// Slices by tower (OWNER = 1, `ppo_update_owner_kernel`; see hop 1): the nblk VALUE workgroups are the only owners, each of a value slice
+// (pass V) and a policy slice (pass P) of all slabs. The slabs' reuse: a workgroup writes slab words of step s + 2 only
+// behind its own hop 2 of step s + 1; that hop needs BOTH passes of step s + 1 of every owner; and an owner finished
+// reading the slabs of step s before it published its sums of step s, which lie before its passes of step s + 1. The
+// sum vector's reuse, where pass V no longer waits for the policy slabs: a pass-V word of step s + 2 needs every value
+// slab of step s + 2, hence every value workgroup past hop 2 of step s + 1, hence every pass-P sum of step s + 1, hence
+// every policy slab of step s + 1, hence every policy workgroup past its hop 2 of step s -- so again nobody still reads
+// the sum vector of step s when a word of step s + 2 lands on it. Sequence numbers, layouts and parities are unchanged.
+template <int NPT, bool TIMING, int KS1, bool LOCAL, bool SHARD, bool SMALL, bool TSPLIT, int OWNER>
 __device__ __forceinline__ void ppo_update_body(
     const ia_policy_desc& d, float* __restrict__ P, float* __restrict__ Pt, float* __restrict__ m, float* __restrict__ v,
     float* __restrict__ nm, float* __restrict__ nv, int32_t* __restrict__ ncount, int update_norm,
@@ -4687,13 +4695,14 @@ __device__ __forceinline__ void ppo_update_body(
   __shared__ int s_ok, s_pub, s_fail, s_pubw[4];
   if (!TIMING) tstamp = nullptr;
   long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  long long tprev = 0;
+  long long tprev = 0, tend = 0;
 #define UPD_TS(k) do { if (tstamp && tid == 0) { const long long tn = wall_clock64(); tacc[k] += tn - tprev; tprev = tn; } } while (0)
   // xcd_pack: the launch has 8x the blocks and only every 8th works, so that all working blocks sit
   // on one XCD (hardware deals consecutive block ids round-robin over the 8 XCDs) and share its L2.
   if (xcd_pack && (blockIdx.x & 7)) return;
   const int vb = xcd_pack ? blockIdx.x >> 3 : blockIdx.x;
   static_assert(!TSPLIT || (!LOCAL && !SHARD && !SMALL), "one tower per workgroup: several gradient workgroups, one process");
+  static_assert(OWNER == 0 || (OWNER == 1 && TSPLIT), "slices by tower: the tower-split form only");
   const int ngw = TSPLIT ? 2 * nblk : nblk;   // gradient workgroups
   const int rb = TSPLIT ? vb >> 1 : vb;       // this gradient workgroup's row block
   const int split_tw = TSPLIT ? (vb & 1) : 0;   // ... and (TSPLIT) its tower
@@ -5191,6 +5200,9 @@ __device__ __forceinline__ void ppo_update_body(
     // (the minibatch ends with a block barrier: the LDS tiles are free; several workgroups: the slab words are on their
     //  way, nobody waits for them here)
     UPD_TS(1);
+    if constexpr (TSPLIT) {   // (measurement build: when the chain ended, on the clock all workgroups share, summed over the steps)
+      if (tstamp && tid == 0) tend += tprev;
+    }
     UPD_TS(7);
     UPD_TS(8);
     float g[NPT];
@@ -5265,6 +5277,18 @@ __device__ __forceinline__ void ppo_update_body(
           ll_store_agent(sums_s + gi, part, lseq);
         }
       };
+      // Who owns which slice (OWNER; TSPLIT: `ia_ppo_update_slice_owner`).
+      //   0  every gradient workgroup takes the range [vb SL, (vb + 1) SL) of the slab itself.
+      //   1  (a pass is a run of SLq consecutive COMPACT indices c0 .. of a set of nset elements; compact index c is
+      //      element c + (c < b1 ? add0 : c < b2 ? add1 : add2)) the elements are dealt by TOWER and only the value
+      //      workgroups own slices: the value workgroup of row block b
+      //      takes slice b of the value elements ([vW1, aW) and [cW, total): complete in every slab as soon as the VALUE
+      //      workgroups' chains end, ahead of the policy workgroups' by their longer loss phase), then slice b of the policy
+      //      elements ([0, vW1), [aW, cW) and the five loss-statistic tail words). A policy workgroup has no pass: behind
+      //      its chain it goes straight to the next rows and hop 2, so neither its prefetch issue nor a poll round begun
+      //      late stands between the step's last slab word and the sum vector.
+      // Either way every element's slab words are summed in slab order 0 .. nblk - 1: the same bits.
+      if constexpr (OWNER == 0) {
       {
       {   // hop 1: this workgroup's slice of every slab. (Tried: sixteen slabs with a 16-lane row per element and the
           // row sums on the DPP path -- no LDS scratch, no barrier --: the loads then touch sixteen cache lines per wave
@@ -5329,6 +5353,95 @@ __device__ __forceinline__ void ppo_update_body(
         }
         for (; j < nblk; ++j) part += red[j * SL + e];
         if (valid_el(gi)) emit(gi, part);
+      }
+      }
+      } else {   // ---- slices by tower, value workgroups only (see above): the same polls, scratch and sums per pass
+      const int npass = split_tw ? 2 : 0;   // (workgroup-uniform: the workgroup's tower)
+      const int nv1 = o.aW - o.vW1, Nv = nv1 + o.total - o.cW, Np = o.vW1 + o.cW - o.aW;
+      for (int pass = 0; pass < npass; ++pass) {
+        const bool pv = pass == 0;   // pass V: the value elements; then pass P: the policy elements + the five tail words
+        const int nset = pv ? Nv : Np + 5;
+        const int b1 = pv ? nv1 : o.vW1, b2 = pv ? 0x7fffffff : Np;
+        const int add0 = pv ? o.vW1 : 0, add1 = pv ? o.cW - nv1 : o.aW - o.vW1, add2 = pv ? add1 : w.P4 - Np;
+        const int SLq = (nset + nblk - 1) / nblk, c0 = rb * SLq;
+        const int roff = pv ? 0 : nblk * ((Nv + nblk - 1) / nblk);   // (pass P: a scratch of its own behind pass V's, no
+                                                                      //  barrier between the passes; <= 2 x 512 NPT floats)
+        const unsigned rcpSLq = 0xffffffffu / (unsigned)SLq + 1u;
+        // (written out at both uses below: as lambdas their closures were left in scratch memory)
+#define IA_SLICE_EL(c) ((c) + ((c) < b1 ? add0 : ((c) < b2 ? add1 : add2)))
+#define IA_SLICE_OWNED(c, gi) ((c) < nset && valid_el(gi))
+      {
+        u64 t[NPT];
+        int gi_[NPT];
+        unsigned need = 0u;
+        int ez;
+        asm volatile("s_mov_b32 %0, 0" : "=s"(ez));
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+          const int f = tid + ez + k * 512;
+          const int j = (int)__umulhi((unsigned)f, rcpSLq), e = f - j * SLq;
+          const int c = c0 + e, gi = IA_SLICE_EL(c);
+          gi_[k] = min(j, nblk - 1) * P8 + min(gi, P8 - 1);
+          if (f < nblk * SLq && IA_SLICE_OWNED(c, gi)) need |= 1u << k;
+        }
+        unsigned it = 0;
+        for (;; ) {
+#pragma unroll
+          for (int k = 0; k < NPT; ++k)   // (unconditional loads at clamped addresses, all in flight together)
+            t[k] = __hip_atomic_load(slabs_s + gi_[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __builtin_amdgcn_sched_barrier(0);
+          bool ok = true;
+#pragma unroll
+          for (int k = 0; k < NPT; ++k) ok = ok && (!((need >> k) & 1u) || (unsigned)(t[k] >> 32) == lseq);
+          if (ok) break;
+          __builtin_amdgcn_s_sleep(1);
+          if ((++it & 255u) == 0 &&
+              (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || wall_clock64() - t0 > local_timeout)) {
+            fail = true;
+            break;
+          }
+        }
+        if (tstamp && tid == 0 && vb == 1) tstamp[40] += it;   // (measurement build: unsuccessful polls, thread 0 of workgroup 1)
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+          const int f = tid + k * 512;
+          if (f < nblk * SLq) red[roff + f] = ((need >> k) & 1u) ? __uint_as_float((unsigned)t[k]) : 0.f;
+        }
+      }
+      UPD_TS(10);
+      if (fail) s_fail = 1;
+      __syncthreads();
+      if (s_fail) {
+        if (tid == 0) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+      }
+      for (int e = tid; e < SLq; e += 512) {   // slice sums in slab order (reads eight at a time), then on their way
+        const int c = c0 + e, gi = IA_SLICE_EL(c);
+        float part = 0.f;
+        int j = 0;
+        for (; j + 8 <= nblk; j += 8) {
+          float tt[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) tt[u] = red[roff + (j + u) * SLq + e];
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int u = 0; u < 8; ++u) part += tt[u];
+        }
+        for (; j < nblk; ++j) part += red[roff + j * SLq + e];
+        if (IA_SLICE_OWNED(c, gi)) emit(gi, part);
+      }
+#undef IA_SLICE_EL
+#undef IA_SLICE_OWNED
+      if (pass + 1 < npass) UPD_TS(11);   // (measurement build: both passes' polls in [10], both passes' sums in [11])
+      }
+      if (npass == 0) {
+        // A policy workgroup: hop 1's polls and barrier are gone, and with them what the staging below took from them --
+        // the prefetched rows and the statistics slot landed (the polls' results were waited for behind them) and waves
+        // 0-2's `s_pubw` published (the barrier). Both by hand; the slice owners need another hand-off and their sums
+        // before the sum vector can arrive, so this wait is not on the step's path.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        UPD_TS(10);
+        __syncthreads();
       }
       }
       if constexpr (SHARD) {   // the ranks' words of this slice, summed in rank order; the global slice published locally
@@ -5641,6 +5754,13 @@ __device__ __forceinline__ void ppo_update_body(
 #undef UPD_TS
   if (tstamp && vb == 0 && tid == 0)
     for (int k = 0; k < 12; ++k) tstamp[k] += tacc[k];
+  if constexpr (TSPLIT) {
+    // (measurement build) workgroup 1, the value twin of row block 0: its own phase ticks in [50..61]; [62 + g]: the sum
+    // over the steps of workgroup g's clock at the end of its chain (g = 0, 1), for the lead of the one over the other
+    if (tstamp && vb == 1 && tid == 0)
+      for (int k = 0; k < 12; ++k) tstamp[50 + k] += tacc[k];
+    if (tstamp && vb < 2 && tid == 0) tstamp[62 + vb] += tend;
+  }
   if (vb == 0 && tid == 0)
     __hip_atomic_store(w.ctrl + 9, lseq_base + (unsigned)n_steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (vb == 0) {
@@ -5680,13 +5800,20 @@ __device__ __forceinline__ void ppo_update_body(
 
 template <int NPT, bool TIMING, int KS1, bool LOCAL, bool SHARD = false, bool SMALL = false>
 __global__ __launch_bounds__(512) void ppo_update_persistent_kernel(IA_UPD_KERNEL_PARAMS) {
-  ppo_update_body<NPT, TIMING, KS1, LOCAL, SHARD, SMALL, false>(IA_UPD_KERNEL_ARGS);
+  ppo_update_body<NPT, TIMING, KS1, LOCAL, SHARD, SMALL, false, 0>(IA_UPD_KERNEL_ARGS);
 }
 
 // One tower per gradient workgroup, two workgroups per row block (see `ppo_update_body`, TSPLIT).
 template <int NPT, bool TIMING, int KS1>
 __global__ __launch_bounds__(512) void ppo_update_split_kernel(IA_UPD_KERNEL_PARAMS) {
-  ppo_update_body<NPT, TIMING, KS1, false, false, false, true>(IA_UPD_KERNEL_ARGS);
+  ppo_update_body<NPT, TIMING, KS1, false, false, false, true, 0>(IA_UPD_KERNEL_ARGS);
+}
+// ... with hop 1's slices dealt by tower and summed by the value workgroups alone (`ia_ppo_update_slice_owner(1)`; see hop 1).
+// A kernel of its own: as a run-time branch in the kernel above, the second ownership cost the chain ~0.8 us per step in
+// BOTH modes (`profiles/ppo_slice_owner.md`).
+template <int NPT, bool TIMING, int KS1>
+__global__ __launch_bounds__(512) void ppo_update_owner_kernel(IA_UPD_KERNEL_PARAMS) {
+  ppo_update_body<NPT, TIMING, KS1, false, false, false, true, 1>(IA_UPD_KERNEL_ARGS);
 }
 #undef IA_UPD_KERNEL_PARAMS
 #undef IA_UPD_KERNEL_ARGS
@@ -6419,6 +6546,13 @@ int g_upd_assume_cus = 0;
 int ia_ppo_update_assume_cus(int n) { g_upd_assume_cus = n; return IA_OK; }
 bool g_upd_tower_split = false;   // (ia_ppo_update_tower_split) two gradient workgroups per row block, one per tower, where they fit
 int ia_ppo_update_tower_split(int on) { g_upd_tower_split = on != 0; return IA_OK; }
+int g_upd_slice_owner = 0;   // (ia_ppo_update_slice_owner) hop 1 of the tower-split form: 0 every gradient workgroup owns a slice,
+                             // 1 the value workgroups own a value and a policy slice each, the policy workgroups none
+int ia_ppo_update_slice_owner(int mode) {
+  if (mode != 0 && mode != 1) return IA_ERR_ARG;
+  g_upd_slice_owner = mode;
+  return IA_OK;
+}
 
 // A whole PPO.train: n_epochs passes over consecutive minibatches of perm[e][T*n_envs] (SB3
 // RolloutBuffer.get order), in ONE persistent launch per <= UPD_MAX_STEPS optimiser steps.
@@ -6476,14 +6610,25 @@ static int ppo_update_launch(const ia_policy_desc* d, float* params, float* para
                          : (shard ? 16 + local * 4 + wide * 2 + ks16 : local * 8 + wide * 4 + timing * 2 + ks16);
   // One tower per gradient workgroup (`ppo_update_split_kernel`): several gradient workgroups of one process, switch on,
   // and -- checked per launch below -- 2 nblk + 1 + 2 n_slices workgroups co-resident; otherwise the form above, unchanged.
-  // [wide * 4 + timing * 2 + ks16]; its own caches of the LDS attribute and the occupancy.
-  static const KernelT split_kernels[8] = {
+  // [owner * 8 + wide * 4 + timing * 2 + ks16]; its own caches of the LDS attribute and the occupancy.
+  // [8 ..]: the same with hop 1's slices by tower on the value workgroups (`ia_ppo_update_slice_owner(1)`)
+  static const KernelT split_kernels[16] = {
       ppo_update_split_kernel<UPD_NPT, false, 8>,      ppo_update_split_kernel<UPD_NPT, false, 16>,
       ppo_update_split_kernel<UPD_NPT, true, 8>,       ppo_update_split_kernel<UPD_NPT, true, 16>,
       ppo_update_split_kernel<UPD_NPT_WIDE, false, 8>, ppo_update_split_kernel<UPD_NPT_WIDE, false, 16>,
-      ppo_update_split_kernel<UPD_NPT_WIDE, true, 8>,  ppo_update_split_kernel<UPD_NPT_WIDE, true, 16>};
+      ppo_update_split_kernel<UPD_NPT_WIDE, true, 8>,  ppo_update_split_kernel<UPD_NPT_WIDE, true, 16>,
+      ppo_update_owner_kernel<UPD_NPT, false, 8>,      ppo_update_owner_kernel<UPD_NPT, false, 16>,
+      ppo_update_owner_kernel<UPD_NPT, true, 8>,       ppo_update_owner_kernel<UPD_NPT, true, 16>,
+      ppo_update_owner_kernel<UPD_NPT_WIDE, false, 8>, ppo_update_owner_kernel<UPD_NPT_WIDE, false, 16>,
+      ppo_update_owner_kernel<UPD_NPT_WIDE, true, 8>,  ppo_update_owner_kernel<UPD_NPT_WIDE, true, 16>};
   const bool want_split = g_upd_tower_split && shard == nullptr && nblk >= 2;
-  const int vi_s = wide * 4 + timing * 2 + ks16;
+  // slices by tower: each of an owner's two passes polls nblk x ceil(set / nblk) words with its parameters-per-thread x 512
+  // lanes (sets: the value elements; the policy elements + 5 loss-statistic words); a pass that does not fit -> ownership 0
+  const PolOff po = pol_offsets(d->obs_dim, d->act_dim, 32, d->discrete);
+  const int n_pol = po.vW1 + (po.cW - po.aW) + 5, n_val = P - (n_pol - 5);
+  const int own_lanes = (wide ? UPD_NPT_WIDE : UPD_NPT) * 512;
+  const bool by_tower = g_upd_slice_owner == 1 && nblk * cdiv(n_pol, nblk) <= own_lanes && nblk * cdiv(n_val, nblk) <= own_lanes;
+  const int vi_s = by_tower * 8 + wide * 4 + timing * 2 + ks16;
   const KernelT kernel = kernels[vi_k];
   static size_t attr_bytes[32] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (bytes > attr_bytes[vi_k]) {
@@ -6537,8 +6682,9 @@ static int ppo_update_launch(const ia_policy_desc* d, float* params, float* para
     int grid = (nblk + 1 + n_slices) * (pack ? 8 : 1);
     KernelT launch_kernel = kernel;
     if (want_split) {   // the same residency test for the wider grid; no room -> the two-tower form (and ITS test) below
-      static int s_dev_cus = 0, s_per_cu[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-      static size_t s_per_cu_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s_attr_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      static int s_dev_cus = 0, s_per_cu[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+      static size_t s_per_cu_bytes[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      static size_t s_attr_bytes[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       if (bytes > s_attr_bytes[vi_s]) {
         const int rc = set_lds(split_kernels[vi_s], bytes);
         if (rc) return rc;

@@ -532,6 +532,9 @@ class PPO(OnPolicyAlgorithm):
         # ... with one tower per gradient workgroup, two workgroups per row block, where several row blocks' worth fit the
         # device (a library-wide switch; bit-identical results). `IA_PPO_TOWER_SPLIT=0`: one per row block
         L.load().ia_ppo_update_tower_split(1 if os.environ.get("IA_PPO_TOWER_SPLIT", "1") != "0" else 0)
+        # ... whose gradient slices every gradient workgroup sums (0) or, dealt by tower, the value workgroups alone (1);
+        # bit-identical too. `IA_PPO_SLICE_OWNER` for the tools; the default follows `profiles/ppo_slice_owner.md`
+        L.load().ia_ppo_update_slice_owner(1 if os.environ.get("IA_PPO_SLICE_OWNER", "0") == "1" else 0)
         self.dp = None  # set by the trainer for data-parallel runs (imitation_amd.distributed.DataParallel)
         # When True, `train()` only ENQUEUES the update and returns; the caller overlaps other GPU
         # work with it and later calls `finalize_train()` (one D2H of the statistics + logging).

@@ -564,7 +564,10 @@ int ia_ppo_minibatch_grad(const ia_policy_desc* d, float* params, float* params_
 int64_t ia_ppo_grad_offset(const ia_policy_desc* d, int batch);
 /* Debug/measurement: when set to a device buffer of 32 int64, block 0 of every ppo_grad launch
  * stores the shader clock at its phase boundaries in [0..11]; ia_ppo_update accumulates 100 MHz ticks
- * per step phase in [0..7] and stores the last step's phase clocks in [16..27] (NULL switches it off). */
+ * per step phase in [0..11] and stores the last step's phase clocks in [16..31] (NULL switches it off); with several gradient
+ * workgroups it also uses [40..49], and the tower-split form [50..61] (the phase ticks of workgroup 1, the value twin of
+ * row block 0) and [62], [63] (workgroups 0 and 1: the 100 MHz clock at the end of the chain, summed over the steps) --
+ * pass 64 int64 to ia_ppo_update's measurement build. */
 int ia_ppo_debug_timing(void* device_buffer_16xi64);
 /* Tuning / measurement: 1 = `ia_ppo_epoch` keeps two launches per minibatch for 64-wide towers (default 0: one launch
  * per epoch, the minibatch steps as phases of a co-resident grid; a row block's two towers
@@ -754,6 +757,14 @@ int ia_ppo_update_assume_cus(int n);
  * their own, and every statistics slice two (even / odd steps) -- 2 nblk + 1 + 2 slices workgroups, all co-resident (same occupancy x compute-unit test; when they do not
  * fit, the call runs the form of 0). Same workspace, bit-identical results. 0: one workgroup per row block. */
 int ia_ppo_update_tower_split(int on);
+/* ia_ppo_update_slice_owner(mode): who sums which slice of the gradient slabs in the tower-split form (no effect on any
+ * other form). 0: every one of the 2 nblk gradient workgroups owns one contiguous slice of the parameter range. 1: the
+ * elements are dealt by tower and only the nblk VALUE workgroups own slices -- slice b of the value elements first (their
+ * slab words depend on the value workgroups' shorter chains only), then slice b of the policy elements and the loss-statistic
+ * words; a policy workgroup goes from its chain straight to the next rows and the sum vector. Every element is still summed in
+ * slab order: bit-identical results, same workspace. Where a pass would not fit the workgroup's lanes, or the split grid is
+ * not co-resident, the call runs the form of 0. Returns IA_ERR_ARG for any other mode. Default 0. */
+int ia_ppo_update_slice_owner(int mode);
 int ia_ppo_update(const ia_policy_desc* d, float* params, float* params_t, float* norm_mean, float* norm_var,
                   int32_t* norm_count, int update_norm, const float* obs, const float* actions, const float* old_logp,
                   const float* advantages, const float* returns, const int64_t* perm, int n_epochs, int T, int n_envs,

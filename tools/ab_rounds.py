@@ -3,7 +3,7 @@ alternating, and times `rounds` rounds of `train()` after a warm-up.
 Usage: python tools/ab_rounds.py <bench variant | P> <attribute>=<a>,<b>[,<c>] [rounds] [repeats]
   attribute: an attribute of the trainer (`disc_behind_ppo`, `disc_round_one_call`, `disc_enqueue_early`) or, with the prefix
   `gen.`, of its PPO (`gen.epochs_one_call`), or `lib.<toggle>`: an integer switch of the library
-  (`lib.ia_ppo_update_xcd_pack`, `lib.ia_ppo_update_tower_split`, `lib.ia_ppo_epoch_split`, `lib.ia_disc_fused_side_reduce`); values: None / True / False / numbers.
+  (`lib.ia_ppo_update_xcd_pack`, `lib.ia_ppo_update_tower_split`, `lib.ia_ppo_update_slice_owner`, `lib.ia_ppo_epoch_split`, `lib.ia_disc_fused_side_reduce`); values: None / True / False / numbers.
   e.g.  python tools/ab_rounds.py P disc_behind_ppo=None,True,False 100
         python tools/ab_rounds.py P_mlp64_1024x16 gen.epochs_one_call=True,False 60 3"""
 import ast

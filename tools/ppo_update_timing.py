@@ -47,6 +47,13 @@ for rep in range(3):
     print(f"unsuccessful polls per step (thread 0 of workgroup 0): hop 1 {polls[0] / steps:.2f}, hop 2 {polls[1] / steps:.2f}")
     print(f"xcd_pack={pack}: train() {1e3 * d:.2f} ms for {steps} steps; per step: " +
           ", ".join(f"{n} {t_ / 100.0 / steps:.2f} us" for n, t_ in zip(names, ticks)))
+    # tower-split form: workgroup 1 (the value twin of row block 0) reports the same phases in [50..61]; [62], [63]: the
+    # shared 100 MHz clock at the end of workgroup 0's / workgroup 1's chain, summed over the steps
+    w1, ends = buf.cpu().numpy()[50:62], buf.cpu().numpy()[62:64]
+    if ends[1]:
+        print(f"  workgroup 1 (value tower, row block 0; IA_PPO_SLICE_OWNER={os.environ.get('IA_PPO_SLICE_OWNER', 'default')}) "
+              "per step: " + ", ".join(f"{n} {t_ / 100.0 / steps:.2f} us" for n, t_ in zip(names, w1) if n != "-"))
+        print(f"  chain end: workgroup 1 leads workgroup 0 by {(ends[0] - ends[1]) / 100.0 / steps:.2f} us per step")
 t = buf.cpu().numpy()[16:32]
 import numpy as np  # noqa: E402
 d = np.diff(np.concatenate([t[:7], t[8:9]]))   # (slot 7 is not stamped: the gradient tiles are one phase)
