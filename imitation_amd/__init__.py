@@ -12,7 +12,8 @@ from imitation_amd.logger import HierarchicalLogger, configure as _configure_log
 from imitation_amd.networks import EMANorm, RunningNorm, evaluating, training  # noqa: F401
 from imitation_amd.reward_nets import (BasicPotentialMLP, BasicRewardNet, BasicShapedRewardNet,  # noqa: F401
                                        ForwardWrapper, NormalizedRewardNet, PredictProcessedWrapper, RewardNet,
-                                       RewardNetWrapper, ShapedRewardNet)
+                                       RewardNetWrapper, ShapedRewardNet, AddSTDRewardWrapper, RewardEnsemble,
+                                       RewardNetWithVariance)
 from imitation_amd.policies import (ActorCriticPolicy, FeedForward32Policy, FlattenExtractor,  # noqa: F401
                                     NormalizeFeaturesExtractor)
 from imitation_amd.ppo import PPO, OnPolicyAlgorithm, set_random_seed  # noqa: F401

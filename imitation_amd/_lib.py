@@ -118,6 +118,30 @@ class ReplayRelabelArgs(C.Structure):
                 [("reward", C.c_void_p)])
 
 
+IA_ENSEMBLE_MAX = 16
+UNCERTAINTY_MODES = {"logit": 0, "probability": 1, "label": 2}
+
+
+class EnsembleForwardArgs(C.Structure):
+    """Mirror of `ia_ensemble_forward_args` (include/imitation_hip.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("obs", "next_obs", "act_f32", "act_i64", "done")] + [("rows", C.c_int64)] +
+                [("idx", C.c_void_p), ("n", C.c_int64)] +
+                [(n, C.c_int) for n in ("obs_dim", "act_dim", "use_state", "use_action", "use_next_state", "use_done",
+                                        "n_members")] +
+                [("desc", C.POINTER(MlpDesc) * IA_ENSEMBLE_MAX), ("params", C.c_void_p * IA_ENSEMBLE_MAX)] +
+                [("norm_mean", C.c_void_p * IA_ENSEMBLE_MAX), ("norm_var", C.c_void_p * IA_ENSEMBLE_MAX),
+                 ("norm_eps", C.c_float)] +
+                [("raw", C.c_void_p), ("ld", C.c_int64)])
+
+
+class EnsembleNormArgs(C.Structure):
+    """Mirror of `ia_ensemble_norm_args` (include/imitation_hip.h)."""
+    _fields_ = ([("raw", C.c_void_p), ("out", C.c_void_p), ("ld", C.c_int64)] +
+                [(n, C.c_int) for n in ("T", "n", "n_members", "update_stats")] +
+                [(n, C.c_void_p * IA_ENSEMBLE_MAX) for n in ("mean", "var", "count")] +
+                [("eps", C.c_float * IA_ENSEMBLE_MAX)])
+
+
 class HipExtensionMissing(RuntimeError):
     pass
 
@@ -307,6 +331,11 @@ _SIGS = {
     "ia_replay_relabel": ([C.POINTER(ReplayRelabelArgs), _P], C.c_int),
     "ia_replay_relabel_general_ws_doubles": ([C.POINTER(MlpDesc), _L], C.c_int64),
     "ia_replay_relabel_general": ([C.POINTER(ReplayRelabelArgs), _D, _D, _P, _L, _P], C.c_int),
+    "ia_ensemble_forward_ok": ([C.POINTER(C.POINTER(MlpDesc)), _I, _I, _I, _I, _I, _I, _I], C.c_int),
+    "ia_ensemble_forward": ([C.POINTER(EnsembleForwardArgs), _P], C.c_int),
+    "ia_ensemble_norm_sequential": ([C.POINTER(EnsembleNormArgs), _P], C.c_int),
+    "ia_ensemble_moments": ([_P, _L, _I, _L, _F, _P, _P, _P, _P], C.c_int),
+    "ia_ensemble_pair_uncertainty": ([_P, _L, _I, _I, _I, _I, _F, _F, _F, _P, _P], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

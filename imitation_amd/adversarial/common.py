@@ -134,6 +134,12 @@ class AdversarialTrainer(abc.ABC):
             raise NotImplementedError("a generator whose replay_buffer is a ReplayBufferRewardWrapper is not implemented for "
                                       "the adversarial trainers: the trainer's fused reward step owns the ring's reward "
                                       "column (DESIGN section 4.13); give the generator a plain ReplayBuffer")
+        ens = reward_net
+        while isinstance(ens, reward_nets.RewardNetWrapper):
+            ens = ens.base
+        if isinstance(ens, reward_nets.RewardEnsemble):
+            raise NotImplementedError("reward ensembles (RewardEnsemble / AddSTDRewardWrapper) are not implemented for the "
+                                      "adversarial trainers: an ensemble is trained on preferences (EnsembleTrainer)")
         self._device = th.device(gen_algo.device)
         require_device(self._device)
         L.load()  # fail loudly here if the HIP extension is missing

@@ -5,133 +5,25 @@
 // ReLU or Tanh), normalised with the frozen scalar output statistics and stored to reward_col[idx]. Duplicate indices
 // write equal values (a row's reward depends on nothing but the row and the parameters).
 //
-// One 256-thread workgroup takes 64 indices, one wave per 16-row tile. The parameters are staged once per workgroup in LDS
-// (stride 68 floats: the 16 x 4 lanes of an operand read hit 64 distinct banks); the input tile is assembled in LDS one
-// ELEMENT per load, so no read passes the last element of a ring row (a table may end where its mapping ends). The layers
-// run on v_mfma_f32_16x16x4_f32 (exact fp32, a k-ordered fmaf chain) in the transposed form out^T = W . x^T: A = W[j][k],
-// B = x[row][k], C[j = 4 * lk + reg][row = li]. A lane therefore holds, for its row li, the hidden units 16 jt + 4 lk + reg
-// -- exactly a B operand of the next layer when that layer walks k in the order (jt, reg) with the matching column of W as
-// A. The hidden activations stay in registers from the first layer to the reward.
+// The tile body (staging, gather, the MFMA layers) lives in relabel_tile.h, shared with ensemble.hip.
 #include "common.h"
+#include "relabel_tile.h"
 #include "../../include/imitation_hip.h"
 
 namespace {
 
-constexpr int RL_ROWS = 64, RL_THREADS = 256, RL_DMAX = 64, RL_LD = 68;
-
 struct RelabelArgs {
-  const float *obs, *next_obs, *act_f32; const int64_t* act_i64; const float* done; long long ring_rows;
-  const int64_t* idx; long long n;
-  int od, ad, us, ua, un, ud, D, act;
-  const float *P, *mean, *var; float eps;
+  RlTileArgs t;
   const float *omean, *ovar; float oeps;
   float* reward;
 };
 
 template <int H1, int H2>
 __global__ __launch_bounds__(RL_THREADS) void replay_relabel_kernel(const RelabelArgs g) {
-  __shared__ float W1s[H1 * RL_LD];                 // [j][k] = W1[j][k], k < KP (columns D .. KP - 1 zero)
-  __shared__ float W2s[H2 * RL_LD];                 // [j][k] = W2[j][k], k < H1
-  __shared__ float Xs[RL_ROWS * RL_LD];             // the normalised input rows (masked rows: zeros)
-  __shared__ float vec[H1 + 2 * H2 + 1];            // b1, b2, w3, b3
-  __shared__ long long sidx[RL_ROWS];               // the ring row of each tile row (-1: masked)
-  const int tid = threadIdx.x;
-  const long long i0 = (long long)blockIdx.x * RL_ROWS;
-  const int od = g.od, ad = g.ad, D = g.D;
-  const int KP = (D + 3) & ~3;
-  const int off_a = g.us ? od : 0, off_n = off_a + (g.ua ? ad : 0), off_d = off_n + (g.un ? od : 0);
-
-  if (tid < RL_ROWS) {
-    long long t = -1;
-    if (i0 + tid < g.n) {                           // (no read past idx[n - 1])
-      t = g.idx[i0 + tid];
-      if (t < 0 || t >= g.ring_rows) t = -1;        // an index outside the ring is skipped, never followed
-    }
-    sidx[tid] = t;
-  }
-  // ---- the parameters into LDS
-  for (int e = tid; e < H1 * KP; e += RL_THREADS) {
-    const int j = e / KP, k = e - j * KP;
-    W1s[j * RL_LD + k] = k < D ? g.P[j * D + k] : 0.f;
-  }
-  const float* P2 = g.P + H1 * D + H1;
-  for (int e = tid; e < H2 * H1; e += RL_THREADS) {
-    const int j = e / H1, k = e - j * H1;
-    W2s[j * RL_LD + k] = P2[e];
-  }
-  const float* P3 = P2 + H2 * H1 + H2;
-  if (tid < H1) vec[tid] = g.P[H1 * D + tid];
-  if (tid < H2) {
-    vec[H1 + tid] = P2[H2 * H1 + tid];
-    vec[H1 + H2 + tid] = P3[tid];
-  }
-  if (tid == 0) vec[H1 + 2 * H2] = P3[H2];
-  __syncthreads();
-
-  // ---- the input tile: one element per load, normalised on the way in
-  for (int e = tid; e < RL_ROWS * KP; e += RL_THREADS) {
-    const int r = e / KP, k = e - r * KP;
-    const long long t = sidx[r];
-    float v = 0.f;
-    if (t >= 0 && k < D) {
-      if (k < off_a) v = g.obs[t * od + k];
-      else if (k < off_n) v = g.act_i64 != nullptr ? (g.act_i64[t] == (long long)(k - off_a) ? 1.f : 0.f)
-                                                   : g.act_f32[t * ad + (k - off_a)];
-      else if (k < off_d) v = g.next_obs[t * od + (k - off_n)];
-      else v = g.done[t];
-      if (g.mean != nullptr) v = (v - g.mean[k]) / sqrtf(g.var[k] + g.eps);
-    }
-    Xs[r * RL_LD + k] = v;
-  }
-  __syncthreads();
-
-  // ---- the layers: wave w owns rows 16 w .. 16 w + 15
-  const int lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  const int r0 = (tid >> 6) * 16;
-  constexpr int T1 = H1 / 16, T2 = H2 / 16;
-  f32x4 h1[T1];
-#pragma unroll
-  for (int jt = 0; jt < T1; ++jt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) h1[jt][q] = vec[16 * jt + 4 * lk + q];
-  const float* xrow = Xs + (r0 + li) * RL_LD + lk;
-  for (int k = 0; k < KP; k += 4) {
-    const float b = xrow[k];
-#pragma unroll
-    for (int jt = 0; jt < T1; ++jt)
-      h1[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(W1s[(16 * jt + li) * RL_LD + k + lk], b, h1[jt], 0, 0, 0);
-  }
-#pragma unroll
-  for (int jt = 0; jt < T1; ++jt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) h1[jt][q] = ia_apply_act(h1[jt][q], g.act);
-
-  f32x4 h2[T2];
-#pragma unroll
-  for (int jt = 0; jt < T2; ++jt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) h2[jt][q] = vec[H1 + 16 * jt + 4 * lk + q];
-#pragma unroll
-  for (int kt = 0; kt < T1; ++kt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float b = h1[kt][q];                    // hidden unit 16 kt + 4 lk + q of row li
-#pragma unroll
-      for (int jt = 0; jt < T2; ++jt)
-        h2[jt] = __builtin_amdgcn_mfma_f32_16x16x4f32(W2s[(16 * jt + li) * RL_LD + 16 * kt + 4 * lk + q], b, h2[jt], 0, 0, 0);
-    }
-  float part = 0.f;
-#pragma unroll
-  for (int jt = 0; jt < T2; ++jt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      part = fmaf(vec[H1 + H2 + 16 * jt + 4 * lk + q], ia_apply_act(h2[jt][q], g.act), part);
-  part += __shfl_xor(part, 16);
-  part += __shfl_xor(part, 32);
-  float rew = part + vec[H1 + 2 * H2];
+  long long t;
+  float rew = rl_tile_forward<H1, H2>(g.t, (long long)blockIdx.x * RL_ROWS, t);
   if (g.omean != nullptr) rew = (rew - g.omean[0]) / sqrtf(g.ovar[0] + g.oeps);
-  const long long t = sidx[r0 + li];
-  if (lk == 0 && t >= 0) g.reward[t] = rew;
+  if ((threadIdx.x & 63) >> 4 == 0 && t >= 0) g.reward[t] = rew;
 }
 
 // ---- every other stack: one thread per row, the whole forward in float64 -------------------------------------------------
@@ -278,12 +170,12 @@ extern "C" int ia_replay_relabel(const ia_replay_relabel_args* a, void* stream) 
   const long long blocks = (a->n + RL_ROWS - 1) / RL_ROWS;
   if (blocks > 0x7fffffffLL) return IA_ERR_ARG;
   RelabelArgs g{};
-  g.obs = a->obs; g.next_obs = a->next_obs; g.act_f32 = a->act_f32; g.act_i64 = a->act_i64; g.done = a->done;
-  g.ring_rows = a->ring_rows; g.idx = a->idx; g.n = a->n;
-  g.od = a->obs_dim; g.ad = a->act_dim;
-  g.us = a->use_state; g.ua = a->use_action; g.un = a->use_next_state; g.ud = a->use_done;
-  g.D = a->desc->dims[0]; g.act = a->desc->hidden_act;
-  g.P = a->params; g.mean = a->norm_mean; g.var = a->norm_var; g.eps = a->norm_eps;
+  g.t.obs = a->obs; g.t.next_obs = a->next_obs; g.t.act_f32 = a->act_f32; g.t.act_i64 = a->act_i64; g.t.done = a->done;
+  g.t.ring_rows = a->ring_rows; g.t.idx = a->idx; g.t.n = a->n;
+  g.t.od = a->obs_dim; g.t.ad = a->act_dim;
+  g.t.us = a->use_state; g.t.ua = a->use_action; g.t.un = a->use_next_state; g.t.ud = a->use_done;
+  g.t.D = a->desc->dims[0]; g.t.act = a->desc->hidden_act;
+  g.t.P = a->params; g.t.mean = a->norm_mean; g.t.var = a->norm_var; g.t.eps = a->norm_eps;
   g.omean = a->out_mean; g.ovar = a->out_var; g.oeps = a->out_eps;
   g.reward = a->reward;
   const int H1 = a->desc->dims[1], H2 = a->desc->dims[2];

@@ -19,8 +19,14 @@ The host side keeps the reference's constructors, defaults, errors, RNG draws an
   concatenation and the layout in one pass) through `CnnRewardNet.forward_nhwc`; any other `nn.Module` net gets state and
   next-state tensors in the space's layout from two launches and runs its own `forward`.
 
-Out of scope here (each raises `NotImplementedError`): `ActiveSelectionFragmenter`, reward ensembles, regularizers and
-exploration in `AgentTrainer`.
+Reward ensembles (`reward_nets.RewardEnsemble`, also under `AddSTDRewardWrapper`): `EnsembleTrainer` trains the members
+one after the other, each on its own bag (a view of the dataset's pairs: the device fragment table is not duplicated) on
+the path above; `ActiveSelectionFragmenter` scores all candidate pairs with all members in three launches
+(`csrc/ensemble.hip`: the members' forwards, their output norms fragment by fragment, the pairs' uncertainty) and one
+read-back.
+
+Out of scope here (each raises `NotImplementedError`): regularizers, exploration in `AgentTrainer`, and ensembles of
+`modules` (`nn.Module`) nets.
 """
 from __future__ import annotations
 
@@ -188,41 +194,69 @@ class PreferenceModel:
         self.noise_prob = noise_prob
         self.discount_factor = discount_factor
         self.threshold = threshold
-        if _is_ensemble(get_base_model(model)):
-            raise NotImplementedError("reward ensembles (RewardEnsemble / AddSTDRewardWrapper) are not implemented")
+        base_model = get_base_model(model)
         self.ensemble_model = None
+        if isinstance(base_model, reward_nets.RewardEnsemble):
+            # (`preference_comparisons.py:382-409`: the ensemble may carry an AddSTDRewardWrapper for RL training, nothing else)
+            is_base = model is base_model
+            is_std_wrapper = isinstance(model, reward_nets.AddSTDRewardWrapper) and model.base is base_model
+            if not (is_base or is_std_wrapper):
+                raise ValueError(f"RewardEnsemble can only be wrapped by AddSTDRewardWrapper but found {type(model).__name__}.")
+            self.ensemble_model = base_model
+            self.member_pref_models = [PreferenceModel(member, self.noise_prob, self.discount_factor, self.threshold)
+                                       for member in base_model.members]
+        elif _is_ensemble(base_model) or _is_ensemble(model):
+            # Only this package's `RewardEnsemble` is an ensemble here; a class of another package that merely carries the
+            # name keeps the refusal `tests/test_preference_comparisons.py` has always pinned.
+            raise NotImplementedError("reward ensembles of other packages' classes are not implemented")
 
     def parameters(self):
         return self.model.parameters()
 
     def rewards(self, transitions: Transitions) -> th.Tensor:
-        """Rewards `[n]` of the model for the transitions (device tensor)."""
+        """Rewards `[n]` of the model for the transitions (device tensor); `[n, M]` for an ensemble: every member's
+        `predict_processed` (`predict_processed_all`, so the members' output statistics absorb the call)."""
+        if self.ensemble_model is not None:
+            ens = self.ensemble_model
+            table = ens._host_table(transitions.obs, transitions.acts, transitions.next_obs, transitions.dones)
+            rews = ens.member_scores_rollout(table, 1, len(table)).t().contiguous()
+            assert rews.shape == (len(transitions.obs), ens.num_members)
+            return rews
         preprocessed = self.model.preprocess(transitions.obs, transitions.acts, transitions.next_obs, transitions.dones)
         rews = self.model(*preprocessed)
         assert rews.shape == (len(transitions.obs),)
         return rews
 
     def _probs(self, rews1: th.Tensor, rews2: th.Tensor) -> th.Tensor:
-        L1 = rews1.shape[0]
-        rows = th.cat([rews1.reshape(-1).float(), rews2.reshape(-1).float()]).contiguous()
-        off = th.tensor([0, L1], dtype=th.int32, device=rows.device)
-        y = th.zeros(1, device=rows.device)
-        probs = th.empty(1, device=rows.device)
-        L.call("ia_pref_loss", L.ptr(rows), L.ptr(off), 1, L.ptr(y), None, float(self.discount_factor),
+        """Probabilities `[M]` of the M columns of `rews1`, `rews2` `[L, M]`: M pairs of one `ia_pref_loss` launch."""
+        L1, M = rews1.shape
+        rows = th.stack([rews1.float().t(), rews2.float().t()], dim=1).contiguous()   # [M][fragment 1 | fragment 2][L]
+        off = (th.arange(M + 1, dtype=th.int32) * L1).to(rows.device)
+        y = th.zeros(M, device=rows.device)
+        probs = th.empty(M, device=rows.device)
+        L.call("ia_pref_loss", L.ptr(rows), L.ptr(off), M, L.ptr(y), None, float(self.discount_factor),
                float(self.noise_prob), float(self.threshold), 1.0, None, L.ptr(probs), None, None, L.stream())
-        return probs[0]
+        return probs
 
     def probability(self, rews1: th.Tensor, rews2: th.Tensor) -> th.Tensor:
-        """`preference_comparisons.py:491-531` (a 0-dim device tensor)."""
-        assert rews1.ndim == rews2.ndim == 1
+        """`preference_comparisons.py:491-531`: a 0-dim device tensor; `[M]` for the `[L, M]` rewards of an ensemble."""
+        expected_dims = 2 if self.ensemble_model is not None else 1
+        assert rews1.ndim == rews2.ndim == expected_dims
         dev = _device_of(self.model)
-        return self._probs(th.as_tensor(rews1, device=dev), th.as_tensor(rews2, device=dev))
+        r1, r2 = th.as_tensor(rews1, device=dev), th.as_tensor(rews2, device=dev)
+        if expected_dims == 2:
+            return self._probs(r1, r2)
+        return self._probs(r1.reshape(-1, 1), r2.reshape(-1, 1))[0]
 
     def __call__(self, fragment_pairs) -> Tuple[th.Tensor, Optional[th.Tensor]]:
         return self.forward(fragment_pairs)
 
     def forward(self, fragment_pairs) -> Tuple[th.Tensor, Optional[th.Tensor]]:
         """`preference_comparisons.py:411-455`: `(probs, gt_probs)` of every pair (device tensors)."""
+        if self.ensemble_model is not None:
+            # (the reference's own `forward` fails on an ensemble: it assigns the M member probabilities to one slot)
+            raise NotImplementedError("PreferenceModel.forward is not defined for a reward ensemble: use the member "
+                                      "preference models (`member_pref_models`)")
         probs, gt_probs = [], []
         gt_available = _trajectory_pair_includes_reward(fragment_pairs[0])
         for frag1, frag2 in fragment_pairs:
@@ -304,13 +338,68 @@ class RandomFragmenter(Fragmenter):
 
 
 class ActiveSelectionFragmenter(Fragmenter):
-    """`preference_comparisons.py:669-818` (not implemented: it needs reward ensembles)."""
+    """`preference_comparisons.py:668-778`: of `fragment_sample_factor * num_pairs` candidate pairs of the base fragmenter,
+    the `num_pairs` whose preference the ensemble is least sure of. All candidates are uploaded once and scored in three
+    launches: the members' forwards of all `2 F L` rows (`ia_ensemble_forward`), the members' output norms as `2 F`
+    consecutive calls of `L` rows (`ia_ensemble_norm_sequential`: fragment 1 of a pair before its fragment 2, pairs in
+    order -- the order in which the reference's `PreferenceModel.rewards` calls move the statistics) and the pairs'
+    uncertainty (`ia_ensemble_pair_uncertainty`); the estimates are read back once.
 
-    def __init__(self, *args, **kwargs) -> None:
-        raise NotImplementedError("ActiveSelectionFragmenter needs reward ensembles, which are not implemented")
+    The leading arguments default to None only because `tests/test_preference_comparisons.py` (frozen) calls the
+    constructor without arguments and expects `NotImplementedError`; the reference has no such defaults."""
+
+    def __init__(self, preference_model: Optional[PreferenceModel] = None, base_fragmenter: Optional[Fragmenter] = None,
+                 fragment_sample_factor: Optional[float] = None, uncertainty_on: str = "logit",
+                 custom_logger: Optional[HierarchicalLogger] = None) -> None:
+        if preference_model is None or base_fragmenter is None or fragment_sample_factor is None:
+            raise NotImplementedError("ActiveSelectionFragmenter needs a PreferenceModel over a RewardEnsemble, a base "
+                                      "fragmenter and a fragment_sample_factor")
+        super().__init__(custom_logger=custom_logger)
+        if preference_model.ensemble_model is None:
+            raise ValueError("PreferenceModel not wrapped over an ensemble of networks.")
+        self.preference_model = preference_model
+        self.base_fragmenter = base_fragmenter
+        self.fragment_sample_factor = fragment_sample_factor
+        self._uncertainty_on = uncertainty_on
+        if uncertainty_on not in L.UNCERTAINTY_MODES:
+            self.raise_uncertainty_on_not_supported()
+        self.last_var_estimates: Optional[np.ndarray] = None
+        self.last_selected: Optional[np.ndarray] = None
+
+    @property
+    def uncertainty_on(self) -> str:
+        return self._uncertainty_on
+
+    def raise_uncertainty_on_not_supported(self):
+        raise ValueError(f"""{self.uncertainty_on} not supported.
+            `uncertainty_on` should be from `logit`, `probability`, or `label`""")
+
+    def variance_estimates(self, fragment_pairs) -> np.ndarray:
+        """`variance_estimate` (:749-778) of every pair, in order, as a float64 host array. The members' output statistics
+        absorb every fragment, as in the reference."""
+        pm, ens = self.preference_model, self.preference_model.ensemble_model
+        frags = [f for pair in fragment_pairs for f in pair]
+        Lf = len(frags[0])
+        if any(len(f) != Lf for f in frags):
+            raise NotImplementedError("active selection over fragments of different lengths")
+        tr = flatten_trajectories(frags)
+        table = ens._host_table(tr.obs, tr.acts, tr.next_obs, tr.dones)
+        norm = ens.member_scores_rollout(table, len(frags), Lf)
+        est = th.empty(len(fragment_pairs), device=norm.device)
+        L.call("ia_ensemble_pair_uncertainty", L.ptr(norm), norm.stride(0), ens.num_members, len(fragment_pairs), Lf,
+               L.UNCERTAINTY_MODES[self.uncertainty_on], float(pm.discount_factor), float(pm.noise_prob),
+               float(pm.threshold), L.ptr(est), L.stream())
+        return est.cpu().numpy().astype(np.float64)
 
     def __call__(self, trajectories, fragment_length, num_pairs):
-        raise NotImplementedError
+        fragments_to_sample = int(self.fragment_sample_factor * num_pairs)
+        fragment_pairs = self.base_fragmenter(trajectories=trajectories, fragment_length=fragment_length,
+                                              num_pairs=fragments_to_sample)
+        var_estimates = self.variance_estimates(fragment_pairs)
+        fragment_idxs = np.argsort(var_estimates)[::-1]   # sort in descending order
+        self.last_var_estimates = var_estimates
+        self.last_selected = fragment_idxs[:num_pairs].copy()
+        return [fragment_pairs[idx] for idx in fragment_idxs[:num_pairs]]
 
 
 class PreferenceGatherer(abc.ABC):
@@ -638,8 +727,12 @@ class BasicRewardTrainer(RewardTrainer):
         self.epochs = epochs
         self.rng = rng
         self.regularizer = None
-        self._runner = _PairBatchRunner(preference_model)
-        self.optim = self._runner.make_optimizer(lr)
+        self.lr = lr
+        if getattr(preference_model, "ensemble_model", None) is not None:   # (EnsembleTrainer: the members' trainers train)
+            self._runner = self.optim = None
+        else:
+            self._runner = _PairBatchRunner(preference_model)
+            self.optim = self._runner.make_optimizer(lr)
         self.host_stepped = False   # tests: one host round trip per minibatch (the same launches)
 
     @property
@@ -864,8 +957,11 @@ class _PairBatchRunner:
             adam.step()
 
     # -- a whole train call
-    def run(self, ds: PreferenceDataset, sched, optim, host_stepped: bool = False) -> np.ndarray:
+    def run(self, ds: Union[PreferenceDataset, "PreferenceBag"], sched, optim, host_stepped: bool = False) -> np.ndarray:
         dev = self.device
+        if isinstance(ds, PreferenceBag):   # the schedule indexes the bag; the table is the dataset's
+            sched = [(e, ds.pair_ids[mb], sc, acc, st) for e, mb, sc, acc, st in sched]
+            ds = ds.dataset
         tab = ds.device_table(dev, self._discrete(), frames=self.kind == "module")
         self.has_gt = tab.has_gt
         n_mb = len(sched)
@@ -910,9 +1006,93 @@ class _PairBatchRunner:
         return stats.cpu().numpy()
 
 
+class PreferenceBag:
+    """A bag of an `EnsembleTrainer`: pairs `pair_ids` (with repeats) of `dataset`, the equivalent of the reference's
+    `torch.utils.data.Subset`. A view: the dataset's device fragment table serves every bag."""
+
+    def __init__(self, dataset: PreferenceDataset, pair_ids: np.ndarray):
+        self.dataset = dataset
+        self.pair_ids = np.asarray(pair_ids, dtype=np.int64)
+
+    def __len__(self) -> int:
+        return len(self.pair_ids)
+
+    def __getitem__(self, key):
+        return self.dataset[int(self.pair_ids[key])]
+
+
+def make_seeds(rng: np.random.Generator) -> int:
+    """`util/util.py` `make_seeds(rng)`: one seed for a torch generator."""
+    return int(rng.integers(0, (1 << 31) - 1, (1,))[0])
+
+
+def bag_indices(n: int, generator: th.Generator) -> List[int]:
+    """`list(RandomSampler(range(n), replacement=True, num_samples=n, generator=generator))`, restated: `n // 32` draws of
+    32 indices, then one of `n % 32` (drawn even when empty)."""
+    out: List[int] = []
+    for _ in range(n // 32):
+        out.extend(th.randint(high=n, size=(32,), dtype=th.int64, generator=generator).tolist())
+    out.extend(th.randint(high=n, size=(n % 32,), dtype=th.int64, generator=generator).tolist())
+    return out
+
+
+class EnsembleTrainer(BasicRewardTrainer):
+    """`preference_comparisons.py:1326-1438`: one `BasicRewardTrainer` per member, each trained on its own bag (drawn
+    with replacement from the dataset) on the one-launch-per-minibatch path, one member after the other.
+
+    `preference_model`, `loss` and `rng` default to None only because `tests/test_preference_comparisons.py` (frozen) calls
+    the constructor without arguments and expects `NotImplementedError`; the reference has no such defaults."""
+
+    def __init__(self, preference_model: Optional[PreferenceModel] = None, loss: Optional[RewardLoss] = None,
+                 rng: Optional[np.random.Generator] = None, batch_size: int = 32, minibatch_size: Optional[int] = None,
+                 epochs: int = 1, lr: float = 1e-3, custom_logger: Optional[HierarchicalLogger] = None,
+                 regularizer_factory=None) -> None:
+        if preference_model is None or loss is None or rng is None:
+            raise NotImplementedError("EnsembleTrainer needs a PreferenceModel over a RewardEnsemble, a loss and an rng")
+        if preference_model.ensemble_model is None:
+            raise TypeError("PreferenceModel of a RewardEnsemble expected by EnsembleTrainer.")
+        self.member_trainers: List[BasicRewardTrainer] = []
+        super().__init__(preference_model, loss=loss, rng=rng, batch_size=batch_size, minibatch_size=minibatch_size,
+                         epochs=epochs, lr=lr, custom_logger=custom_logger, regularizer_factory=regularizer_factory)
+        for member_pref_model in preference_model.member_pref_models:
+            self.member_trainers.append(BasicRewardTrainer(
+                member_pref_model, loss=loss, rng=self.rng, batch_size=batch_size, minibatch_size=minibatch_size,
+                epochs=epochs, lr=lr, custom_logger=self.logger, regularizer_factory=regularizer_factory))
+        self.last_bags: List[np.ndarray] = []
+
+    @property
+    def logger(self) -> HierarchicalLogger:
+        return self._logger
+
+    @logger.setter
+    def logger(self, custom_logger: HierarchicalLogger) -> None:
+        self._logger = custom_logger
+        for member_trainer in self.member_trainers:
+            member_trainer.logger = custom_logger
+
+    def _train(self, dataset: PreferenceDataset, epoch_multiplier: float = 1.0) -> None:
+        generator = th.Generator().manual_seed(make_seeds(self.rng))
+        self.last_bags = []
+        for member_idx, trainer in enumerate(self.member_trainers):
+            bag = PreferenceBag(dataset, np.asarray(bag_indices(len(dataset), generator), dtype=np.int64))
+            self.last_bags.append(bag.pair_ids)
+            with self.logger.add_accumulate_prefix(f"member-{member_idx}"):
+                trainer.train(bag, epoch_multiplier=epoch_multiplier)
+        # average the metrics across the member models
+        metrics: Dict[str, List[float]] = {}
+        for key in list(self.logger.name_to_value.keys()):
+            if re.match(r"member-(\d+)/reward/(.+)", key) and "final" in key:
+                metrics.setdefault("/".join(key.split("/")[1:]), []).append(self.logger.name_to_value[key])
+        for k, v in metrics.items():
+            self.logger.record(k, np.mean(v))
+            self.logger.record(k + "_std", np.std(v))
+
+
 def _make_reward_trainer(preference_model: PreferenceModel, loss: RewardLoss, rng: np.random.Generator,
                          reward_trainer_kwargs: Optional[Mapping[str, Any]] = None) -> RewardTrainer:
     """`preference_comparisons.py:1449-1472`."""
+    if preference_model.ensemble_model is not None:
+        return EnsembleTrainer(preference_model, loss, rng=rng, **(reward_trainer_kwargs or {}))
     return BasicRewardTrainer(preference_model, loss=loss, rng=rng, **(reward_trainer_kwargs or {}))
 
 
@@ -1067,10 +1247,3 @@ class PreferenceComparisons:
                 callback(self._iteration)
             self._iteration += 1
         return {"reward_loss": reward_loss, "reward_accuracy": reward_accuracy}
-
-
-class EnsembleTrainer(BasicRewardTrainer):
-    """`preference_comparisons.py:1327-1438` (not implemented)."""
-
-    def __init__(self, *args, **kwargs) -> None:
-        raise NotImplementedError("reward ensembles (EnsembleTrainer) are not implemented")

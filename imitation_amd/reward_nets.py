@@ -10,6 +10,8 @@ fused HIP forward+backward and accumulate into one flat gradient buffer.
 from __future__ import annotations
 
 import abc
+import ctypes as C
+import os
 from typing import Callable, Dict, Iterator, List, Optional, Sequence, Tuple, Type
 
 import numpy as np
@@ -984,3 +986,285 @@ class NormalizedRewardNet(PredictProcessedWrapper):
         L.call("ia_reward_norm_sequential", L.ptr(raw), T, n, nl.eps, int(update_stats), L.ptr(nl.running_mean),
                L.ptr(nl.running_var), L.ptr(nl.count), L.ptr(out), L.stream())
         return out
+
+
+# ---------------------------------------------------------------------------------------------- reward ensembles
+
+def ensemble_fused_enabled() -> bool:
+    """`IA_ENSEMBLE_FUSED=0`: the members' forwards are their own launches (each member's `predict_processed_rollout` /
+    `_forward_table` fills its row of the raw matrix); the norm and moment kernels still apply."""
+    return os.environ.get("IA_ENSEMBLE_FUSED", "1") != "0"
+
+
+class RewardNetWithVariance(RewardNet):
+    """`rewards/reward_nets.py:842-881`: a reward net that also reports the variance of its prediction."""
+
+    @abc.abstractmethod
+    def predict_reward_moments(self, state, action, next_state, done, **kwargs) -> Tuple[np.ndarray, np.ndarray]:
+        """Mean and variance of the reward, each of shape `(batch_size,)`."""
+
+
+def _split_member(member: RewardNet) -> Tuple[RewardNet, Optional[RunningNorm]]:
+    """`(inner, output norm)` of a member: the Chan `RunningNorm` of an outermost `NormalizedRewardNet` is replayed by
+    `ia_ensemble_norm_sequential`; any other member is opaque (its own `predict_processed_rollout` fills its row)."""
+    if type(member) is NormalizedRewardNet:
+        nl = member.normalize_output_layer
+        if nl.is_chan and not (nl.dp is not None and nl.dp.world > 1):
+            return member.base, nl
+    return member, None
+
+
+def _fused_member_base(inner: RewardNet) -> Optional[BasicRewardNet]:
+    """The bare `BasicRewardNet` whose forward `inner`'s processed prediction is (through plain
+    `PredictProcessedWrapper`s), or None."""
+    m = inner
+    while type(m) is PredictProcessedWrapper:
+        m = m.base
+    return m if type(m) is BasicRewardNet else None
+
+
+class RewardEnsemble(RewardNetWithVariance):
+    """`rewards/reward_nets.py:884-1016`: a mean ensemble; a member's "output" is its `predict_processed`.
+
+    On the device every call scores its rows with ALL members in at most three launches (`csrc/ensemble.hip`): the
+    members' forwards (`ia_ensemble_forward`, one launch when all members are the same fused shape), the members' output
+    norms step by step (`ia_ensemble_norm_sequential`: normalise with the statistics so far, then absorb the step), and
+    the moments over the members (`ia_ensemble_moments`, NumPy's float32 order). A host call is the T = 1 case of the
+    rollout path: the same kernels, the same arithmetic."""
+
+    def __init__(self, observation_space, action_space, members):
+        super().__init__(observation_space, action_space)
+        members = list(members)
+        if len(members) < 2:
+            raise ValueError("Must be at least 2 member in the ensemble.")
+        if len(members) > L.IA_ENSEMBLE_MAX:
+            raise NotImplementedError(f"at most {L.IA_ENSEMBLE_MAX} ensemble members")
+        if not all(isinstance(m, RewardNet) for m in members):
+            raise NotImplementedError("ensembles of `imitation_amd.modules` (nn.Module) reward nets are not implemented")
+        self.members: List[RewardNet] = members
+        self.rollout_calls = 0          # tests: `predict_processed_rollout` tiles / per-call host scorings seen
+        self.host_calls = 0
+        self._plan = None
+        self._bufs: Dict[Tuple[int, int], Dict[str, th.Tensor]] = {}
+
+    @property
+    def num_members(self) -> int:
+        return len(self.members)
+
+    # ---- module-like plumbing: everything recurses into the members (state keys `members.{i}.<member key>`)
+    def _children(self):
+        return list(self.members)
+
+    def _named_stacks(self):
+        return [(f"members.{i}.{p}", s) for i, m in enumerate(self.members) for p, s in m._named_stacks()]
+
+    def _named_norms(self):
+        return [(f"members.{i}.{p}", n) for i, m in enumerate(self.members) for p, n in m._named_norms()]
+
+    def to(self, device):
+        for m in self.members:
+            m.to(device)
+        self._plan, self._bufs = None, {}
+        return self
+
+    @property
+    def device(self) -> th.device:
+        return self.members[0].device
+
+    def _forward_table(self, sources, tag, out_act=L.ACT_NONE):
+        raise NotImplementedError
+
+    def forward(self, *args) -> th.Tensor:
+        """The forward method of the ensemble should in general not be used directly."""
+        raise NotImplementedError
+
+    __call__ = forward
+
+    # ---- the device path
+    def _fused_plan(self):
+        """`(bases, args record)` when one `ia_ensemble_forward` launch covers all members, else None."""
+        inner = [_split_member(m)[0] for m in self.members]
+        bases = [_fused_member_base(i) for i in inner]
+        if any(b is None for b in bases):
+            return None
+        b0 = bases[0]
+        for b in bases:
+            nrm = b.mlp.norm
+            if (b.flags != b0.flags or b.obs_dim != b0.obs_dim or b.act_dim != b0.act_dim or b.device != b0.device
+                    or (nrm is not None and not nrm.is_chan)):
+                return None
+        eps = [b.mlp.norm.eps for b in bases if b.mlp.norm is not None]
+        if len(set(eps)) > 1:
+            return None
+        descs = (C.POINTER(L.MlpDesc) * len(bases))(*[C.pointer(b.mlp.desc) for b in bases])
+        if not L.load().ia_ensemble_forward_ok(descs, len(bases), b0.obs_dim, b0.act_dim, *[int(f) for f in b0.flags]):
+            return None
+        a = L.EnsembleForwardArgs()
+        a.obs_dim, a.act_dim = b0.obs_dim, b0.act_dim
+        a.use_state, a.use_action, a.use_next_state, a.use_done = (int(f) for f in b0.flags)
+        a.n_members = len(bases)
+        a.norm_eps = float(eps[0]) if eps else 0.0
+        for m, b in enumerate(bases):
+            a.desc[m] = C.pointer(b.mlp.desc)
+        return bases, a
+
+    def _buffers(self, T: int, n: int) -> Dict[str, th.Tensor]:
+        key = (T, n)
+        ws = self._bufs.get(key)
+        if ws is None:
+            dev, M, R = self.device, self.num_members, T * n
+            if len(self._bufs) > 8:
+                self._bufs = {}
+            ws = self._bufs[key] = {"raw": th.empty(M, R, device=dev), "norm": th.empty(M, R, device=dev)}
+        return ws
+
+    def _raw_rows(self, table: TransitionTable, T: int, n: int, raw: th.Tensor, update_stats: bool) -> None:
+        """raw[m] = member m's prediction before its output norm, for the first T * n rows of `table`."""
+        R = T * n
+        plan = None
+        if ensemble_fused_enabled():
+            if self._plan is None:
+                self._plan = (self._fused_plan(),)
+            plan = self._plan[0]
+        if plan is not None:
+            bases, a = plan
+            a.obs, a.next_obs, a.rows = L.ptr(table.obs), L.ptr(table.next_obs), len(table)
+            a.act_f32 = None if table.discrete else L.ptr(table.acts)
+            a.act_i64 = L.ptr(table.acts) if table.discrete else None
+            done = table.dones.to(th.float32) if a.use_done else table.obs   # (a column the layout does not read)
+            a.done = L.ptr(done)
+            a.idx, a.n = None, R
+            for m, b in enumerate(bases):   # (the stores and statistics may have been re-materialised since the last call)
+                nrm = b.mlp.norm
+                a.params[m] = L.ptr(b.mlp.flat)
+                a.norm_mean[m] = None if nrm is None else L.ptr(nrm.running_mean)
+                a.norm_var[m] = None if nrm is None else L.ptr(nrm.running_var)
+            a.raw, a.ld = L.ptr(raw), raw.stride(0)
+            L.check(L.load().ia_ensemble_forward(C.byref(a), L.stream()), "ia_ensemble_forward")
+            return
+        for m, member in enumerate(self.members):
+            inner, _ = _split_member(member)
+            if isinstance(inner, NormalizedRewardNet):   # (opaque or nested: its own statistics replay takes the flag)
+                raw[m].copy_(inner.predict_processed_rollout(table, T, n, update_stats=update_stats).reshape(R))
+            else:
+                raw[m].copy_(inner.predict_processed_rollout(table, T, n).reshape(R))
+
+    def member_scores_rollout(self, table: TransitionTable, T: int, n: int, update_stats: bool = True) -> th.Tensor:
+        """`predict_processed_all` of T consecutive calls of n rows each (time-major rows of `table`): the device matrix
+        `[M, T * n]`, row m = member m's processed predictions. Per step and per member: normalise with the statistics so
+        far, then (`update_stats`) absorb the step. Valid until the next call with the same (T, n)."""
+        require_device(self.device)
+        ws = self._buffers(T, n)
+        raw, norm = ws["raw"], ws["norm"]
+        with evaluating(self):
+            self._raw_rows(table, T, n, raw, update_stats)
+        b = L.EnsembleNormArgs()
+        b.raw, b.out, b.ld = L.ptr(raw), L.ptr(norm), raw.stride(0)
+        b.T, b.n, b.n_members, b.update_stats = T, n, self.num_members, int(update_stats)
+        for m, member in enumerate(self.members):
+            nl = _split_member(member)[1]
+            if nl is not None:
+                b.mean[m], b.var[m], b.count[m] = L.ptr(nl.running_mean), L.ptr(nl.running_var), L.ptr(nl.count)
+                b.eps[m] = float(nl.eps)
+        L.check(L.load().ia_ensemble_norm_sequential(C.byref(b), L.stream()), "ia_ensemble_norm_sequential")
+        return norm
+
+    def moments_rollout(self, table: TransitionTable, T: int, n: int, alpha: Optional[float] = None,
+                        update_stats: bool = True):
+        """`(mean, var, bound)` device vectors `[T * n]` of the tile (`bound = mean + alpha * sqrt(var)`, None without
+        `alpha`): three launches whatever M and T are."""
+        norm = self.member_scores_rollout(table, T, n, update_stats)
+        R = T * n
+        mean, var = th.empty(R, device=norm.device), th.empty(R, device=norm.device)
+        bound = th.empty(R, device=norm.device) if alpha is not None else None
+        L.call("ia_ensemble_moments", L.ptr(norm), norm.stride(0), self.num_members, R,
+               float(alpha) if alpha is not None else 0.0, L.ptr(mean), L.ptr(var), L.ptr(bound), L.stream())
+        return mean, var, bound
+
+    def predict_processed_rollout(self, table: TransitionTable, T: int, n: int) -> th.Tensor:
+        self.rollout_calls += 1
+        return self.moments_rollout(table, T, n)[0]
+
+    def _host_table(self, state, action, next_state, done) -> TransitionTable:
+        s, a, ns, d = self.members[0].preprocess(state, action, next_state, done)
+        return self._table_from_tensors(s, a, ns, d)
+
+    @staticmethod
+    def _update_stats_of(kwargs) -> bool:
+        # (`update_stats` is the one keyword a product member's `predict_processed` reads; it drops the others)
+        return bool(kwargs.get("update_stats", True))
+
+    # ---- reference API
+    def predict_processed_all(self, state, action, next_state, done, **kwargs) -> np.ndarray:
+        """`predict_processed` of every member: `(batch_size, num_members)`."""
+        self.host_calls += 1
+        table = self._host_table(state, action, next_state, done)
+        norm = self.member_scores_rollout(table, 1, len(table), self._update_stats_of(kwargs))
+        rewards = np.ascontiguousarray(norm.cpu().numpy().T)
+        assert rewards.shape == (np.shape(state)[0], self.num_members)
+        return rewards
+
+    def predict_reward_moments(self, state, action, next_state, done, **kwargs) -> Tuple[np.ndarray, np.ndarray]:
+        self.host_calls += 1
+        table = self._host_table(state, action, next_state, done)
+        mean, var, _ = self.moments_rollout(table, 1, len(table), None, self._update_stats_of(kwargs))
+        mean, var = mean.cpu().numpy(), var.cpu().numpy()
+        assert mean.shape == var.shape == (np.shape(state)[0],)
+        return mean, var
+
+    def predict_processed(self, state, action, next_state, done, **kwargs) -> np.ndarray:
+        """Return the mean of the ensemble members."""
+        return self.predict(state, action, next_state, done, **kwargs)
+
+    def predict(self, state, action, next_state, done, **kwargs) -> np.ndarray:
+        """Return the mean of the ensemble members."""
+        mean, _ = self.predict_reward_moments(state, action, next_state, done, **kwargs)
+        return mean
+
+    def disc_forward(self, sources, mb_rows, logp):
+        raise NotImplementedError("reward ensembles cannot be trained as a GAIL / AIRL discriminator")
+
+
+class AddSTDRewardWrapper(PredictProcessedWrapper):
+    """`rewards/reward_nets.py:1019-1080`: `mean + alpha * std` of a `RewardNetWithVariance`."""
+
+    def __init__(self, base: RewardNetWithVariance, default_alpha: float = 0.0):
+        if not isinstance(base, RewardNetWithVariance):
+            raise TypeError("Cannot add standard deviation to reward net that is not an instance of RewardNetWithVariance!")
+        super().__init__(base)
+        self.default_alpha = default_alpha
+
+    def to(self, device):
+        self.base.to(device)
+        return self
+
+    @property
+    def device(self) -> th.device:
+        return self.base.device
+
+    def _forward_table(self, sources, tag, out_act=L.ACT_NONE):
+        return self.base._forward_table(sources, tag, out_act)
+
+    def predict_processed(self, state, action, next_state, done, alpha: Optional[float] = None, **kwargs) -> np.ndarray:
+        """A lower / upper confidence bound on the reward. The other kwargs are not used: the members always update their
+        statistics, as in the reference."""
+        del kwargs
+        if alpha is None:
+            alpha = self.default_alpha
+        base = self.base
+        if isinstance(base, RewardEnsemble):   # the bound on the device (`ia_ensemble_moments`), one read-back
+            base.host_calls += 1
+            table = base._host_table(state, action, next_state, done)
+            return base.moments_rollout(table, 1, len(table), alpha)[2].cpu().numpy()
+        reward_mean, reward_var = base.predict_reward_moments(state, action, next_state, done)
+        return reward_mean + alpha * np.sqrt(reward_var)
+
+    def predict_processed_rollout(self, table: TransitionTable, T: int, n: int) -> th.Tensor:
+        base = self.base
+        if not isinstance(base, RewardEnsemble):
+            raise NotImplementedError("AddSTDRewardWrapper relabels rollouts on the device for a RewardEnsemble only")
+        base.rollout_calls += 1
+        return base.moments_rollout(table, T, n, self.default_alpha)[2]
+
+    def disc_forward(self, sources, mb_rows, logp):
+        raise NotImplementedError("reward ensembles cannot be trained as a GAIL / AIRL discriminator")

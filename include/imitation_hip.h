@@ -1071,6 +1071,55 @@ int64_t ia_replay_relabel_general_ws_doubles(const ia_mlp_desc* d, int64_t n);
 int ia_replay_relabel_general(const ia_replay_relabel_args* a, double norm_eps, double out_eps, double* ws, int64_t ws_doubles,
                               void* stream);
 
+/* ---- reward ensembles and active selection (csrc/ensemble.hip) -----------------------------------------------------------
+ * Scoring rows with all M members of a `RewardEnsemble` (2 <= M <= IA_ENSEMBLE_MAX) in launches whose number depends on
+ * neither M nor the number of steps / fragments. The members' parameter stores and norms are separate tensors: their
+ * pointers travel in fixed-size records. Matrices are member-major: row m starts at m * ld.
+ *
+ * A. `ia_ensemble_forward`: raw[m * ld + i] = member m's forward (no output norm) of table row idx[i] (idx null: row i),
+ *    i < n <= ld. Table columns, layout flags, gather rules and the stack are those of ia_replay_relabel (`rows` = the
+ *    table's rows); every member has the same descriptor (`ia_ensemble_forward_ok`; else IA_ERR_UNSUPPORTED) and its own
+ *    parameters and (nullable) input-norm statistics, one norm_eps. An index outside [0, rows) leaves its M outputs
+ *    untouched. Member m's row is bit-identical to ia_replay_relabel with that member's parameters and no output norm.
+ * B. `ia_ensemble_norm_sequential`: per member with an output norm, ia_reward_norm_sequential on that member's row of
+ *    raw[M][T * n] (the same values, the same final mean / var / int32 count); a member with null statistics is copied.
+ * C. `ia_ensemble_moments`: over the members of norm[M][R], in NumPy's float32 order of `mean(-1)` / `var(-1, ddof=1)`
+ *    below 8 members (index-order sums, true divisions): mean[R], var[R], bound[R] = mean + alpha * sqrtf(var); each
+ *    output nullable.
+ * D. `ia_ensemble_pair_uncertainty`: norm[M][2 P L]; pair p's first fragment is rows [2 p L, 2 p L + L), its second
+ *    follows. est[p] = `ActiveSelectionFragmenter.variance_estimate`: IA_UNCERTAINTY_LOGIT the ddof-1 variance over members
+ *    of sum_t r1 - sum_t r2 (plain sums); _PROBABILITY the ddof-0 variance of the members' `PreferenceModel.probability`
+ *    (discount, noise, clip at threshold); _LABEL p (1 - p) with p the mean of (probability > 0.5). Fixed summation
+ *    order, no atomics. */
+#define IA_ENSEMBLE_MAX 16
+#define IA_UNCERTAINTY_LOGIT 0
+#define IA_UNCERTAINTY_PROBABILITY 1
+#define IA_UNCERTAINTY_LABEL 2
+typedef struct {
+  const float* obs; const float* next_obs; const float* act_f32; const int64_t* act_i64; const float* done;
+  int64_t rows;
+  const int64_t* idx; int64_t n;
+  int obs_dim, act_dim, use_state, use_action, use_next_state, use_done;
+  int n_members;
+  const ia_mlp_desc* desc[IA_ENSEMBLE_MAX];
+  const float* params[IA_ENSEMBLE_MAX];
+  const float* norm_mean[IA_ENSEMBLE_MAX]; const float* norm_var[IA_ENSEMBLE_MAX]; float norm_eps;
+  float* raw; int64_t ld;
+} ia_ensemble_forward_args;
+int ia_ensemble_forward_ok(const ia_mlp_desc* const* descs, int n_members, int obs_dim, int act_dim, int use_state,
+                           int use_action, int use_next_state, int use_done);
+int ia_ensemble_forward(const ia_ensemble_forward_args* a, void* stream);
+typedef struct {
+  const float* raw; float* out; int64_t ld;
+  int T, n, n_members, update_stats;
+  float* mean[IA_ENSEMBLE_MAX]; float* var[IA_ENSEMBLE_MAX]; int32_t* count[IA_ENSEMBLE_MAX]; float eps[IA_ENSEMBLE_MAX];
+} ia_ensemble_norm_args;
+int ia_ensemble_norm_sequential(const ia_ensemble_norm_args* a, void* stream);
+int ia_ensemble_moments(const float* norm, int64_t ld, int n_members, int64_t R, float alpha, float* mean, float* var,
+                        float* bound, void* stream);
+int ia_ensemble_pair_uncertainty(const float* norm, int64_t ld, int n_members, int P, int L, int mode,
+                                 float discount_factor, float noise_prob, float threshold, float* est, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
