@@ -142,6 +142,9 @@ class EnsembleNormArgs(C.Structure):
                 [("eps", C.c_float * IA_ENSEMBLE_MAX)])
 
 
+REG_OK, REG_LAMBDA_ZERO, REG_LAMBDA_NEGATIVE, REG_LOSS_NEGATIVE = 0, 1, 2, 3
+
+
 class HipExtensionMissing(RuntimeError):
     pass
 
@@ -336,6 +339,9 @@ _SIGS = {
     "ia_ensemble_norm_sequential": ([C.POINTER(EnsembleNormArgs), _P], C.c_int),
     "ia_ensemble_moments": ([_P, _L, _I, _L, _F, _P, _P, _P, _P], C.c_int),
     "ia_ensemble_pair_uncertainty": ([_P, _L, _I, _I, _I, _I, _F, _F, _F, _P, _P], C.c_int),
+    "ia_reg_lp": ([_P, _I, _I, _P, _P, _F, _P, _P], C.c_int),
+    "ia_reg_weight_decay": ([_P, _I, _P, _D, _P], C.c_int),
+    "ia_reg_lambda_update": ([_P, _P, _P, _I, _P, _I, _I, _D, _D, _D, _P, _P, _P], C.c_int),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -25,8 +25,16 @@ the path above; `ActiveSelectionFragmenter` scores all candidate pairs with all 
 (`csrc/ensemble.hip`: the members' forwards, their output norms fragment by fragment, the pairs' uncertainty) and one
 read-back.
 
-Out of scope here (each raises `NotImplementedError`): regularizers, exploration in `AgentTrainer`, and ensembles of
-`modules` (`nn.Module`) nets.
+Regularizers (`imitation_amd.regularization`: `LpRegularizer`, `WeightDecayRegularizer`, the `IntervalParamScaler` lambda
+schedule, the train / validation split that feeds it): lambda is one device `float64` scalar of the regularizer. After
+each training minibatch's backward `ia_reg_lp` adds the penalty's gradient and writes `regularized_loss` (or
+`ia_reg_weight_decay` decays the weights), each epoch's validation minibatches run forward and loss only, and
+`ia_reg_lambda_update` applies the schedule to the scalar at the epoch's end, so a regularised `train()` call is still one
+enqueue and one read-back. Any other `LambdaUpdater` callable runs on the host: one synchronisation per epoch.
+
+Out of scope here (each raises `NotImplementedError`): user-defined `Regularizer` subclasses and factories that are not a
+`regularization.RegularizerFactory` of a shipped class (the product path has no autograd a custom penalty could run
+under), exploration in `AgentTrainer`, and ensembles of `modules` (`nn.Module`) nets.
 """
 from __future__ import annotations
 
@@ -41,7 +49,7 @@ import numpy as np
 import torch as th
 
 from imitation_amd import _lib as L
-from imitation_amd import modules, ops, reward_nets, rollout
+from imitation_amd import modules, ops, regularization, reward_nets, rollout
 from imitation_amd.data_types import ExpertIndexStream, TrajectoryWithRew, Transitions, flatten_trajectories
 from imitation_amd.logger import HierarchicalLogger, configure as configure_logger
 from imitation_amd.networks import HipAdam, TransitionTable, gather_concat, training
@@ -682,6 +690,25 @@ def loader_epoch_permutations(n: int, epochs: int) -> List[np.ndarray]:
     return out
 
 
+def loader_epoch_permutations_split(n_train: int, n_val: int, epochs: int) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """`loader_epoch_permutations` for a training and a validation `DataLoader(shuffle=True)` iterated one after the other
+    in every epoch, as `BasicRewardTrainer._train` does with a validation split: per epoch the train loader's base seed,
+    its sampler's seed and `randperm(n_train)`, then the same three draws of the validation loader."""
+    out = []
+    for _ in range(epochs):
+        (train,) = loader_epoch_permutations(n_train, 1)
+        (val,) = loader_epoch_permutations(n_val, 1)
+        out.append((train, val))
+    return out
+
+
+def random_split_indices(n: int, val_length: int, generator: th.Generator) -> Tuple[np.ndarray, np.ndarray]:
+    """The subset indices of `torch.utils.data.random_split(range(n), [n - val_length, val_length], generator)`: one
+    `randperm(n)`, its first `n - val_length` entries train, the rest validate."""
+    perm = th.randperm(n, generator=generator).numpy()
+    return perm[:n - val_length], perm[n - val_length:]
+
+
 class RewardTrainer(abc.ABC):
     """`preference_comparisons.py:1094-1136`."""
 
@@ -709,14 +736,21 @@ class RewardTrainer(abc.ABC):
 class BasicRewardTrainer(RewardTrainer):
     """`preference_comparisons.py:1139-1324` on the device. The whole `train` call is enqueued at once: the pair order
     of every epoch is drawn first, each minibatch's statistics row (loss, accuracy, gt_reward_loss) stays on the device,
-    and the rows are read back once and replayed into the logger in the reference's order."""
+    and the rows are read back once and replayed into the logger in the reference's order.
+
+    `regularizer_factory`: a `regularization.RegularizerFactory` (what `LpRegularizer.create(...)` /
+    `WeightDecayRegularizer.create(...)` return) of one of these two classes. Anything else -- a bare function, a factory
+    of a user subclass -- raises `NotImplementedError`: the penalty runs as a HIP kernel between the backward pass and the
+    optimiser step, and the product path has no autograd under which a Python penalty could run. A deliberate cut."""
 
     def __init__(self, preference_model: PreferenceModel, loss: RewardLoss, rng: np.random.Generator,
                  batch_size: int = 32, minibatch_size: Optional[int] = None, epochs: int = 1, lr: float = 1e-3,
                  custom_logger: Optional[HierarchicalLogger] = None, regularizer_factory=None) -> None:
         super().__init__(preference_model, custom_logger)
-        if regularizer_factory is not None:
-            raise NotImplementedError("reward regularizers are not implemented")
+        if regularizer_factory is not None and not (isinstance(regularizer_factory, regularization.RegularizerFactory)
+                                                    and regularizer_factory.cls in regularization.SHIPPED):
+            raise NotImplementedError("reward regularizers other than a RegularizerFactory of LpRegularizer or "
+                                      "WeightDecayRegularizer (their `create(...)`) are not implemented")
         if not isinstance(loss, CrossEntropyRewardLoss):
             raise NotImplementedError("only CrossEntropyRewardLoss is implemented on the device")
         self.loss = loss
@@ -726,49 +760,93 @@ class BasicRewardTrainer(RewardTrainer):
             raise ValueError("Batch size must be a multiple of minibatch size.")
         self.epochs = epochs
         self.rng = rng
-        self.regularizer = None
         self.lr = lr
         if getattr(preference_model, "ensemble_model", None) is not None:   # (EnsembleTrainer: the members' trainers train)
             self._runner = self.optim = None
         else:
             self._runner = _PairBatchRunner(preference_model)
             self.optim = self._runner.make_optimizer(lr)
+        # (an EnsembleTrainer's own regularizer has no optimiser: it exists for its construction-time log record)
+        self.regularizer = (regularizer_factory(optimizer=self.optim, logger=self.logger)
+                            if regularizer_factory is not None else None)
         self.host_stepped = False   # tests: one host round trip per minibatch (the same launches)
+        self.last_split: Optional[Tuple[np.ndarray, np.ndarray]] = None
+        self.last_lambda_history: Optional[np.ndarray] = None
 
     @property
     def requires_regularizer_update(self) -> bool:
-        return False
+        return self.regularizer is not None and self.regularizer.val_split is not None
 
     def _schedule(self, n: int, epochs: int):
         """[(epoch, pairs of the minibatch, loss scale, accumulate, step after it)] of `epochs` passes."""
         out = []
         for epoch, perm in enumerate(loader_epoch_permutations(n, epochs)):
-            acc = 0
-            for s in range(0, n, self.minibatch_size):
-                mb = perm[s:s + self.minibatch_size]
-                first = acc == 0
-                acc += len(mb)
-                step = acc >= self.batch_size or s + self.minibatch_size >= n
-                out.append((epoch, mb, len(mb) / self.batch_size, not first, step))
-                if acc >= self.batch_size:
-                    acc = 0
+            self._schedule_epoch(out, epoch, perm)
         return out
 
+    def _schedule_split(self, train_idx: np.ndarray, val_idx: np.ndarray, epochs: int):
+        """The schedule with a validation split: per epoch the training minibatches over `train_idx` (entries as in
+        `_schedule`), then the validation minibatches over `val_idx` as `(epoch, pairs, None, None, None)` (forward and
+        loss only), then the lambda update `(epoch, None, None, None, None)`."""
+        out = []
+        for epoch, (perm, vperm) in enumerate(loader_epoch_permutations_split(len(train_idx), len(val_idx), epochs)):
+            self._schedule_epoch(out, epoch, train_idx[perm])
+            for s in range(0, len(val_idx), self.minibatch_size):
+                out.append((epoch, val_idx[vperm[s:s + self.minibatch_size]], None, None, None))
+            out.append((epoch, None, None, None, None))
+        return out
+
+    def _schedule_epoch(self, out, epoch: int, perm: np.ndarray) -> None:
+        n, acc = len(perm), 0
+        for s in range(0, n, self.minibatch_size):
+            mb = perm[s:s + self.minibatch_size]
+            first = acc == 0
+            acc += len(mb)
+            step = acc >= self.batch_size or s + self.minibatch_size >= n
+            out.append((epoch, mb, len(mb) / self.batch_size, not first, step))
+            if acc >= self.batch_size:
+                acc = 0
+
     def _train(self, dataset: PreferenceDataset, epoch_multiplier: float = 1.0) -> None:
+        reg = self.regularizer
+        split = None
+        if reg is not None and reg.val_split is not None:
+            val_length = int(len(dataset) * reg.val_split)
+            train_length = len(dataset) - val_length
+            if val_length < 1 or train_length < 1:
+                raise ValueError("Not enough data samples to split into training and validation, "
+                                 "or the validation split is too large/small. "
+                                 "Make sure you've generated enough initial preference data. "
+                                 "You can adjust this through initial_comparison_frac in "
+                                 "PreferenceComparisons.")
+            split = random_split_indices(len(dataset), val_length, th.Generator().manual_seed(make_seeds(self.rng)))
+        self.last_split = split
         epochs = round(self.epochs * epoch_multiplier)
         assert epochs > 0, "Must train for at least one epoch."
-        sched = self._schedule(len(dataset), epochs)
-        stats = self._runner.run(dataset, sched, self.optim, host_stepped=self.host_stepped)
+        sched = self._schedule(len(dataset), epochs) if split is None else self._schedule_split(*split, epochs)
+        if reg is None:
+            stats = self._runner.run(dataset, sched, self.optim, host_stepped=self.host_stepped)
+        else:
+            stats = self._runner.run(dataset, sched, self.optim, host_stepped=self.host_stepped, reg=reg)
+            self.last_lambda_history = self._runner.last_hist
         gt = self._runner.has_gt
         epoch_num = epochs - 1
+        lp = isinstance(reg, regularization.LossRegularizer)
+        rows = iter(stats)
         with self.logger.accumulate_means("reward"):
-            for (epoch, _, _, _, _), row in zip(sched, stats):
+            for epoch, mb, scale, _, _ in sched:
                 with self.logger.add_key_prefix(f"epoch-{epoch}"):
-                    with self.logger.add_key_prefix("train"):
+                    if mb is None:   # the epoch's lambda update
+                        self.logger.record("regularization_lambda", float(self._runner.last_hist[epoch][0]))
+                        continue
+                    row = next(rows)
+                    with self.logger.add_key_prefix("train" if scale is not None else "val"):
                         self.logger.record("loss", float(row[0]))
                         self.logger.record("accuracy", float(row[1]))
                         if gt:
                             self.logger.record("gt_reward_loss", float(row[2]))
+                    if lp and scale is not None:
+                        self.logger.record("regularized_loss", float(row[3]))
         keys = list(self.logger.name_to_value.keys())
         outer_prefix = self.logger.get_accumulate_prefixes()
         for key in keys:
@@ -957,16 +1035,35 @@ class _PairBatchRunner:
             adam.step()
 
     # -- a whole train call
-    def run(self, ds: Union[PreferenceDataset, "PreferenceBag"], sched, optim, host_stepped: bool = False) -> np.ndarray:
+    def _segments(self, optim, reg) -> th.Tensor:
+        """The regularizer's segment table: the flat parameter / gradient buffers of a product net's store, or every
+        `nn.Parameter` of the optimiser (Lp: a parameter without a gradient gets a zero one first, the penalty gives it one
+        in the reference; the gradient tensors then stay in place for the whole call, see `run`)."""
+        if self.kind != "module":
+            return regularization.segment_table([(optim.flat, optim.grad)])
+        params = [q for group in optim.param_groups for q in group["params"]]
+        if reg.needs_grads:
+            for q in params:
+                if q.grad is None:
+                    q.grad = th.zeros_like(q, memory_format=th.contiguous_format)
+        return regularization.segment_table([(q.data, q.grad if reg.needs_grads else None) for q in params])
+
+    def run(self, ds: Union[PreferenceDataset, "PreferenceBag"], sched, optim, host_stepped: bool = False,
+            reg: Optional[regularization.Regularizer] = None) -> np.ndarray:
+        """Enqueues the schedule `sched` (`BasicRewardTrainer._schedule` / `_schedule_split`) and returns the statistics
+        rows of its minibatches, in order: (loss, accuracy, gt_reward_loss) and, with a regularizer `reg`, regularized_loss.
+        With a lambda schedule `last_hist` holds one row (lambda after, train_loss, val_loss, error code) per epoch."""
         dev = self.device
         if isinstance(ds, PreferenceBag):   # the schedule indexes the bag; the table is the dataset's
-            sched = [(e, ds.pair_ids[mb], sc, acc, st) for e, mb, sc, acc, st in sched]
+            sched = [(e, ds.pair_ids[mb] if mb is not None else None, sc, acc, st) for e, mb, sc, acc, st in sched]
             ds = ds.dataset
         tab = ds.device_table(dev, self._discrete(), frames=self.kind == "module")
         self.has_gt = tab.has_gt
-        n_mb = len(sched)
+        batches = [it for it in sched if it[1] is not None]
+        n_mb = len(batches)
+        n_upd = len(sched) - n_mb
         # every minibatch's rows, pair offsets and preferences in one upload
-        parts = [tab.batch(mb) for _, mb, _, _, _ in sched]
+        parts = [tab.batch(mb) for _, mb, _, _, _ in batches]
         row_at = np.zeros(n_mb + 1, dtype=np.int64)
         np.cumsum([len(r) for r, _ in parts], out=row_at[1:])
         off_at = np.zeros(n_mb + 1, dtype=np.int64)
@@ -974,36 +1071,107 @@ class _PairBatchRunner:
         rows_all = th.as_tensor(np.concatenate([r for r, _ in parts])).to(dev)
         off_all = th.as_tensor(np.concatenate([o for _, o in parts]).astype(np.int32)).to(dev)
         pair_at = np.zeros(n_mb + 1, dtype=np.int64)
-        np.cumsum([len(mb) for _, mb, _, _, _ in sched], out=pair_at[1:])
-        y_all = th.as_tensor(np.concatenate([tab.prefs[mb] for _, mb, _, _, _ in sched])).to(dev)
+        np.cumsum([len(mb) for _, mb, _, _, _ in batches], out=pair_at[1:])
+        y_all = th.as_tensor(np.concatenate([tab.prefs[mb] for _, mb, _, _, _ in batches])).to(dev)
         gt_all = tab.gt[rows_all] if tab.has_gt else None
-        stats = th.zeros(n_mb, 3, device=dev)
         d_all = th.empty(int(row_at[-1]), device=dev)
-        for k, (_, mb, scale, accumulate, step) in enumerate(sched):
+        self.last_hist = None
+        if reg is None:
+            stats = th.zeros(n_mb, 3, device=dev)
+        else:
+            # one buffer, one read-back: the lambda history (doubles, first) and the four-column statistics
+            buf = th.zeros(32 * n_upd + 16 * n_mb, dtype=th.uint8, device=dev)
+            hist = buf[:32 * n_upd].view(th.float64).view(n_upd, 4)
+            stats = buf[32 * n_upd:].view(th.float32).view(n_mb, 4)
+            hist_host = np.zeros((n_upd, 4))
+            if n_upd and reg.device_schedule and not isinstance(reg.lambda_, float):
+                raise ValueError("lambda_ must be a float")   # (`IntervalParamScaler.__call__`; a double on the device)
+            lam = reg.device_lambda(dev)
+            segs = self._segments(optim, reg)
+            scales = th.as_tensor(np.array([1.0 if sc is None else sc for _, _, sc, _, _ in batches],
+                                           np.float32)).to(dev)
+        k = ep0 = val0 = 0   # the minibatch; the first training and the first validation minibatch of the epoch
+        for epoch, mb, scale, accumulate, step in sched:
+            if mb is None:   # the epoch's lambda update on rows [ep0, val0) and [val0, k)
+                if reg.device_schedule:
+                    regularization.lambda_update(lam, reg.lambda_updater, stats[ep0:val0], scales[ep0:val0],
+                                                 stats[val0:k], hist[epoch], hist[epoch - 1] if epoch else None)
+                else:
+                    # any other updater is a host function: one synchronisation per epoch
+                    loss = stats[ep0:k, 0].cpu().numpy()
+                    sc = np.array([b[2] for b in batches[ep0:val0]], np.float32)
+                    train_loss = val_loss = 0.0
+                    for j in range(val0 - ep0):
+                        train_loss += float(loss[j] * sc[j])
+                    for j in range(val0 - ep0, k - ep0):
+                        val_loss += float(loss[j])
+                    reg.lambda_ = reg.lambda_updater(reg.lambda_, train_loss, val_loss)
+                    hist_host[epoch] = (reg.lambda_, train_loss, val_loss, 0.0)
+                ep0 = val0 = k
+                continue
             r0, r1 = int(row_at[k]), int(row_at[k + 1])
             rows_d = rows_all[r0:r1]
             off_d = off_all[int(off_at[k]):int(off_at[k + 1])]
             y = y_all[int(pair_at[k]):int(pair_at[k + 1])]
             gt = gt_all[r0:r1] if gt_all is not None else None
             off = parts[k][1]
-            if self.kind == "module":
+            if scale is None:   # validation: forward and loss only (in training mode, as in the reference)
+                if self.kind == "module":
+                    with th.no_grad():
+                        rew = self._module_rewards(tab, rows_d, off)
+                        _, st, _ = ops.preference_loss(rew, off_d, y, gt, self.pm.discount_factor, self.pm.noise_prob,
+                                                       self.pm.threshold)
+                    stats[k, :3].copy_(st)
+                else:
+                    rew = self._product_forward(tab, rows_d, off)
+                    self._launch_loss(rew, off_d, y, gt, 1.0, None, stats[k])
+                k += 1
+            elif self.kind == "module":
                 if not accumulate:
-                    optim.zero_grad()
+                    # (a loss regularizer's segment table points at the gradient tensors: they are zeroed in place)
+                    optim.zero_grad(set_to_none=False) if reg is not None and reg.needs_grads else optim.zero_grad()
                 rew = self._module_rewards(tab, rows_d, off)
                 loss, st, _ = ops.preference_loss(rew, off_d, y, gt, self.pm.discount_factor, self.pm.noise_prob,
                                                   self.pm.threshold)
-                stats[k].copy_(st)
+                stats[k, :3].copy_(st)
                 (loss * scale).backward()
+                if reg is not None:
+                    reg.launch(segs, stats[k], scale)
                 if step:
                     optim.step()
+                k += 1
+                val0 = k
             else:
                 rew = self._product_forward(tab, rows_d, off)
                 d = d_all[r0:r1]
                 self._launch_loss(rew, off_d, y, gt, scale, d, stats[k])
-                self._product_backward(d, accumulate, optim if step else None)
+                if reg is None:
+                    self._product_backward(d, accumulate, optim if step else None)
+                else:
+                    # the penalty (or the decay) sits between the backward pass and the optimiser step: the step
+                    # cannot be fused into the gradient reduction
+                    self._product_backward(d, accumulate, None)
+                    reg.launch(segs, stats[k], scale)
+                    if step:
+                        optim.step()
+                k += 1
+                val0 = k
             if host_stepped:
                 th.cuda.current_stream().synchronize()
-        return stats.cpu().numpy()
+        if reg is None:
+            return stats.cpu().numpy()
+        host = buf.cpu().numpy()
+        out = host[32 * n_upd:].view(np.float32).reshape(n_mb, 4).copy()
+        if n_upd:
+            if reg.device_schedule:
+                self.last_hist = host[:32 * n_upd].view(np.float64).reshape(n_upd, 4).copy()
+                reg.refresh_lambda(self.last_hist[-1][0])
+                bad = self.last_hist[:, 3] != 0
+                if bad.any():
+                    raise ValueError(regularization.ERROR_MESSAGES[int(self.last_hist[bad][0][3])])
+            else:
+                self.last_hist = hist_host
+        return out
 
 
 class PreferenceBag:

@@ -1120,6 +1120,38 @@ int ia_ensemble_moments(const float* norm, int64_t ld, int n_members, int64_t R,
 int ia_ensemble_pair_uncertainty(const float* norm, int64_t ld, int n_members, int P, int L, int mode,
                                  float discount_factor, float noise_prob, float threshold, float* est, void* stream);
 
+/* Reward regularizers (regularization/regularizers.py, regularization/updaters.py). Lambda is ONE device double that the
+ * three kernels read (C: update), so a regularised training call needs no host round trip. A and B walk a device table of
+ * segments (parameter pointer, gradient pointer, float count) in ONE workgroup: deterministic, no atomics. A segment needs
+ * 4-byte alignment only: 16-byte accesses start at w's next 16-byte boundary when g is aligned like w modulo 16, scalar
+ * heads and tails cover the rest (a segment whose g is aligned differently is walked element by element).
+ *
+ * A. `ia_reg_lp` (LpRegularizer._loss_penalty + LossRegularizer.regularize_and_backward), integer p >= 1, l = (float)*lambda:
+ *      S = sum over all segments of |w|^p (fp32, fixed order);   g += (l * p) * (sign(w) * |w|^(p-1)), sign(0) = 0;
+ *      stats (nullable, a minibatch's statistics row of >= 4 floats): stats[3] = stats[0] * loss_scale + l * S
+ *      (`regularized_loss`); s_out (nullable) <- S. A segment with a null gradient pointer counts in S only.
+ * B. `ia_reg_weight_decay` (WeightDecayRegularizer): w = w + c * w, c = (float)(-*lambda * lr) formed in double; the
+ *    product and the sum round once each. Gradient pointers are not read (may be null).
+ * C. `ia_reg_lambda_update` (IntervalParamScaler.__call__ in double, on *lambda in place): train_loss = sum_k
+ *    (double)(train_stats[k * stride] * train_scales[k]) (the fp32 product, as `loss *= len / batch_size` forms it),
+ *    val_loss = sum_k (double)val_stats[k * stride], both in index order. row[4] <- (lambda after, train_loss, val_loss,
+ *    code). Where the host version raises, code is IA_REG_LAMBDA_ZERO (|lambda| < DBL_EPSILON), IA_REG_LAMBDA_NEGATIVE or
+ *    IA_REG_LOSS_NEGATIVE and lambda is left alone; a non-zero code in prev_row (nullable: the previous epoch's row) is
+ *    carried over and lambda left alone as well. */
+#define IA_REG_OK 0
+#define IA_REG_LAMBDA_ZERO 1
+#define IA_REG_LAMBDA_NEGATIVE 2
+#define IA_REG_LOSS_NEGATIVE 3
+typedef struct {
+  float* w; float* g; int64_t n;
+} ia_reg_segment;
+int ia_reg_lp(const ia_reg_segment* segs, int n_segs, int p, const double* lambda, float* stats, float loss_scale,
+              float* s_out, void* stream);
+int ia_reg_weight_decay(const ia_reg_segment* segs, int n_segs, const double* lambda, double lr, void* stream);
+int ia_reg_lambda_update(double* lambda, const float* train_stats, const float* train_scales, int n_train,
+                         const float* val_stats, int n_val, int stride, double scaling_factor, double lower,
+                         double upper, const double* prev_row, double* row, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
