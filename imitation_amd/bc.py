@@ -209,12 +209,9 @@ class BC:
         self._steps += 1
         bc1 = 1.0 - self.betas[0] ** self._steps
         bc2 = 1.0 - self.betas[1] ** self._steps
-        rn = pol.features_extractor.normalize
         B = len(idx)
-        L.call("ia_ppo_minibatch", C.byref(pol.desc), L.ptr(pol._flat), L.ptr(pol._flat_t),
-               L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
-               L.ptr(rn.count) if rn else None, 0, L.ptr(obs), L.ptr(acts), L.ptr(logp), L.ptr(self._ones),
-               L.ptr(self._zeros), L.ptr(self._rows), B, 1, B, 0, 0.2, self.ent_weight, 0.0, 3.0e38,
+        L.call("ia_ppo_minibatch", *pol._ppo_source_args(0, (obs, acts, logp, self._ones, self._zeros), self._rows),
+               B, 1, B, 0, 0.2, self.ent_weight, 0.0, 3.0e38,
                L.ptr(self._exp_avg), L.ptr(self._exp_avg_sq), self.betas[0], self.betas[1], self.eps,
                self.lr / bc1, math.sqrt(bc2), L.ptr(self._ws), L.ptr(self._stats), L.stream())
         return logp, ent
@@ -234,14 +231,11 @@ class BC:
                 self._acc.add_(pol._flat, alpha=self.l2_weight * share)
             return logp, ent
         _, logp, ent = pol.evaluate_actions(obs, acts)
-        rn = pol.features_extractor.normalize
         B = len(idx)
         P = pol._flat.numel()
-        L.call("ia_ppo_minibatch_grad", C.byref(pol.desc), L.ptr(pol._flat), L.ptr(pol._flat_t),
-               L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
-               L.ptr(rn.count) if rn else None, 0, L.ptr(obs), L.ptr(acts), L.ptr(logp),
-               L.ptr(self._ones * share), L.ptr(self._zeros), L.ptr(self._rows), B, 1, B, 0, 0.2,
-               self.ent_weight * share, 0.0, L.ptr(self._ws), L.stream())
+        L.call("ia_ppo_minibatch_grad",
+               *pol._ppo_source_args(0, (obs, acts, logp, self._ones * share, self._zeros), self._rows),
+               B, 1, B, 0, 0.2, self.ent_weight * share, 0.0, L.ptr(self._ws), L.stream())
         self._acc += self._ws[self._grad_off:self._grad_off + P]
         if self.l2_weight:
             self._acc.add_(pol._flat, alpha=self.l2_weight * share)   # d/dw of l2_weight * sum(w^2) / 2, this share

@@ -5823,21 +5823,102 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 template <int H>
 size_t lds_bytes() { return Lds<H>::total * sizeof(float); }
 
+// Host state of one kernel's launches. One function- or file-local static per kernel (or per kernel-table entry), touched
+// only by the code that launches that kernel: no shared map, no lock.
+struct LaunchSlot {
+  size_t lds_set = 0;      // largest dynamic-LDS size the kernel's attribute has been raised to
+  int per_cu = -1;         // workgroups per compute unit by the occupancy query (-1: not asked yet) ...
+  size_t per_cu_lds = 0;   // ... and the dynamic-LDS size it was asked at
+};
+
+// raises the kernel's dynamic-LDS limit to `bytes`, unless an earlier call has already set as much
 template <typename K>
-int set_lds(K kern, size_t bytes) {
+int ensure_lds(LaunchSlot& s, K kern, size_t bytes) {
+  if (bytes <= s.lds_set) return IA_OK;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)bytes);
-  return e == hipSuccess ? IA_OK : (int)e;
+  if (e != hipSuccess) return (int)e;
+  s.lds_set = bytes;
+  return IA_OK;
 }
 
-bool g_epoch_split = false;  // tuning/debug: two launches per minibatch for 64-wide towers too
-bool g_epoch_whole = false;  // tuning/debug: the one-launch epoch with whole row-block workgroups (8 waves, both towers)
-bool g_epoch_barriers = false;   // tuning/debug: the one-tower epoch kernel with grid barriers instead of the word exchange
-bool g_epoch_chain2 = true;      // the word-exchange epoch kernel with round 5's transposed register-resident chain (observation
-                                 // widths <= 32); false: round 4's gradient body everywhere
-bool g_epoch_rows32 = true;      // round 6: that kernel on 32-row blocks where they fit (false: 64-row blocks, eight waves, everywhere)
-bool g_epoch_quarters = true;    // round 6: ... with eight waves per 32-row block (two row groups x four feature quarters)
-long long* g_epoch_dbg = nullptr;  // measurement: phase ticks of workgroup 0 of ppo_epoch_persistent_kernel
+// compute units of the current device (0: the query failed)
+int device_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 0;
+    cus = n;
+  }
+  return cus;
+}
+
+// IA_OK when `grid` workgroups of `kern` (`threads` threads, `bytes` of dynamic LDS) are resident at once on `cus` compute
+// units, IA_ERR_UNSUPPORTED when not. Kernels whose workgroups wait for each other need that, and a plain launch performs
+// no such check (a cooperative launch costs +15-19 us per launch, MI355X_MICROARCH.md "coop-launch"): workgroups per CU
+// by the occupancy query (LDS-bound: one) times the CU count.
+template <typename K>
+int fits_resident(LaunchSlot& s, K kern, int threads, size_t bytes, long long grid, int cus) {
+  if (s.per_cu < 0 || s.per_cu_lds != bytes) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), threads, bytes) != hipSuccess)
+      return IA_ERR_ARG;
+    s.per_cu = nb;
+    s.per_cu_lds = bytes;
+  }
+  return (long long)s.per_cu * cus >= grid ? IA_OK : IA_ERR_UNSUPPORTED;
+}
+
+// Adam's bias corrections of optimiser step `step` (1-based), formed in double exactly as torch.optim.Adam does
+struct AdamScalars { float step_size, bc2_sqrt; };
+inline AdamScalars adam_scalars(int64_t step, double lr, double beta1, double beta2) {
+  return {(float)(lr / (1.0 - pow(beta1, (double)step))), (float)sqrt(1.0 - pow(beta2, (double)step))};
+}
+
+// Row blocks the word areas of the word-exchange epoch kernels are laid out for: 32-row blocks (twice the slabs) where at
+// most `max32` of them cover a minibatch of `batch` rows, 64-row blocks otherwise. The workspace (`ia_ppo_ws_floats`) is
+// sized for max32 = 32, the most `plan_epoch` ever passes.
+struct LlBlocks { int n; bool rows32; };
+inline LlBlocks epoch_ll_blocks(int batch, int P, int max32) {
+  const int r32 = epoch_ll_row_blocks(cdiv(batch, 32), P);
+  if (r32 <= max32) return {r32, true};
+  return {epoch_ll_row_blocks(cdiv(batch, ROWS), P), false};
+}
+
+// One launch of an inference kernel on `n` rows, 64 per workgroup. The kernel is a template argument, so that each kernel
+// has its own launch slot.
+template <auto Kern, typename... A>
+int launch_rows(int threads, size_t bytes, int n, void* stream, A... args) {
+  static LaunchSlot slot;
+  if (int rc = ensure_lds(slot, Kern, bytes)) return rc;
+  hipLaunchKernelGGL(Kern, dim3(cdiv(n, ROWS)), dim3(threads), bytes, (hipStream_t)stream, args...);
+  IA_CHECK_LAUNCH();
+  return IA_OK;
+}
+template <int H>
+constexpr size_t alds_bytes() { return ALds<H>::total * sizeof(float); }   // (the matrix-core kernels: 512 threads)
+
+// f(std::integral_constant<int, hidden>) for the tower widths the fused kernels are built for
+template <typename F>
+int by_hidden(int hidden, F f) {
+  switch (hidden) {
+    case 32: return f(std::integral_constant<int, 32>());
+    case 64: return f(std::integral_constant<int, 64>());
+    default: return IA_ERR_UNSUPPORTED;
+  }
+}
+
+// Every workgroup of a mailbox kernel stays resident for the whole rollout and the host waits for ALL of them at every
+// step: more workgroups than the device can hold at once would leave the surplus waiting for the residents forever.
+// (One workgroup per CU is always possible.)
+int mailbox_resident(int n) {
+  const int cus = device_cus();
+  if (cus <= 0) return IA_ERR_ARG;
+  return cdiv(n, ROWS) > cus ? IA_ERR_UNSUPPORTED : IA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -5858,24 +5939,11 @@ int ia_policy_act(const ia_policy_desc* d, const float* params, const float* par
                   const float* norm_var, const float* obs, int n, const float* noise, const float* low,
                   const float* high, float* actions, float* clipped, float* values, float* logp, void* stream) {
   if (!pol_ok(d) || n <= 0) return IA_ERR_ARG;
-  int rc;
-  if (d->hidden == 32) {
-    static bool attr = false;
-    const size_t bytes = ALds<32>::total * sizeof(float);
-    if (!attr) { if ((rc = set_lds(policy_act_mfma_kernel<32, false>, bytes))) return rc; attr = true; }
-    hipLaunchKernelGGL((policy_act_mfma_kernel<32, false>), dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream, *d,
-                       params, params_t, norm_mean, norm_var, obs, n, noise, low, high, actions, clipped, values, logp);
-  } else if (d->hidden == 64) {
-    static bool attr = false;
-    const size_t bytes = ALds<64>::total * sizeof(float);
-    if (!attr) { if ((rc = set_lds(policy_act_mfma_kernel<64, false>, bytes))) return rc; attr = true; }
-    hipLaunchKernelGGL((policy_act_mfma_kernel<64, false>), dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream, *d,
-                       params, params_t, norm_mean, norm_var, obs, n, noise, low, high, actions, clipped, values, logp);
-  } else {
-    return IA_ERR_UNSUPPORTED;
-  }
-  IA_CHECK_LAUNCH();
-  return IA_OK;
+  return by_hidden(d->hidden, [&](auto h) {
+    constexpr int H = decltype(h)::value;
+    return launch_rows<policy_act_mfma_kernel<H, false>>(512, alds_bytes<H>(), n, stream, *d, params, params_t, norm_mean,
+                                                         norm_var, obs, n, noise, low, high, actions, clipped, values, logp);
+  });
 }
 
 // The rollout's act steps as ONE resident launch driven through flags in pinned host memory (policy_rollout_mailbox_kernel).
@@ -5889,128 +5957,53 @@ int ia_policy_rollout_mailbox(const ia_policy_desc* d, const float* params, cons
                               void* stream) {
   if (!pol_ok(d) || n <= 0 || T <= 0 || !ready || !done || !obs || !actions || !clipped || !values || !logp)
     return IA_ERR_ARG;
-  if (d->hidden != 32 && d->hidden != 64) return IA_ERR_UNSUPPORTED;
-  {
-    // every workgroup stays resident for the whole rollout and the host waits for ALL of them at every step: more
-    // workgroups than the device can hold at once would leave the surplus waiting for the residents forever
-    static int dev_cus = 0;
-    if (dev_cus == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return IA_ERR_ARG;
-    }
-    if (cdiv(n, ROWS) > dev_cus) return IA_ERR_UNSUPPORTED;   // (one workgroup per CU is always possible)
-  }
+  if (int rc = mailbox_resident(n)) return rc;
   ActMailbox mb{obs, s_obs, noise, s_noise, actions, s_act, clipped, s_clip, values, s_val, logp, s_lp, last_val, T,
                 reinterpret_cast<const int*>(ready), reinterpret_cast<int*>(done), (long long)(timeout_s * 1e8)};
-  int rc;
-  if (d->hidden == 32) {
-    static bool attr = false;
-    const size_t bytes = ALds<32>::total * sizeof(float);
-    if (!attr) { if ((rc = set_lds(policy_rollout_mailbox_kernel<32>, bytes))) return rc; attr = true; }
-    hipLaunchKernelGGL((policy_rollout_mailbox_kernel<32>), dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream,
-                       *d, params, params_t, norm_mean, norm_var, n, low, high, mb);
-  } else {
-    static bool attr = false;
-    const size_t bytes = ALds<64>::total * sizeof(float);
-    if (!attr) { if ((rc = set_lds(policy_rollout_mailbox_kernel<64>, bytes))) return rc; attr = true; }
-    hipLaunchKernelGGL((policy_rollout_mailbox_kernel<64>), dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream,
-                       *d, params, params_t, norm_mean, norm_var, n, low, high, mb);
-  }
-  IA_CHECK_LAUNCH();
-  return IA_OK;
+  return by_hidden(d->hidden, [&](auto h) {
+    constexpr int H = decltype(h)::value;
+    return launch_rows<policy_rollout_mailbox_kernel<H>>(512, alds_bytes<H>(), n, stream, *d, params, params_t, norm_mean,
+                                                         norm_var, n, low, high, mb);
+  });
 }
 
 int ia_policy_logits_mailbox(const ia_policy_desc* d, const float* params, const float* params_t, const float* norm_mean,
                              const float* norm_var, int n, const float* obs, int64_t s_obs, float* logits, float* values,
                              int64_t s_val, int T, const int32_t* ready, int32_t* done, double timeout_s, void* stream) {
   if (!pol_ok(d) || n <= 0 || T <= 0 || !ready || !done || !obs || !logits) return IA_ERR_ARG;
-  {
-    static int dev_cus = 0;
-    if (dev_cus == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return IA_ERR_ARG;
-    }
-    if (cdiv(n, ROWS) > dev_cus) return IA_ERR_UNSUPPORTED;   // (every workgroup must be resident: see the act mailbox)
-  }
+  if (int rc = mailbox_resident(n)) return rc;
   LogitsMailbox mb{obs, s_obs, logits, values, s_val, T, reinterpret_cast<const int*>(ready),
                    reinterpret_cast<int*>(done), (long long)(timeout_s * 1e8)};
-  int rc;
-  {   // the MFMA body (both towers of 64 rows per 512-thread workgroup)
-    if (d->hidden == 32) {
-      const size_t bytes = ALds<32>::total * sizeof(float);
-      if ((rc = set_lds(policy_logits_mailbox_mfma_kernel<32>, bytes))) return rc;
-      hipLaunchKernelGGL(policy_logits_mailbox_mfma_kernel<32>, dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream, *d,
-                         params, params_t, norm_mean, norm_var, n, mb);
-    } else {
-      const size_t bytes = ALds<64>::total * sizeof(float);
-      if ((rc = set_lds(policy_logits_mailbox_mfma_kernel<64>, bytes))) return rc;
-      hipLaunchKernelGGL(policy_logits_mailbox_mfma_kernel<64>, dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream, *d,
-                         params, params_t, norm_mean, norm_var, n, mb);
-    }
-    IA_CHECK_LAUNCH();
-    return IA_OK;
-  }
-  return IA_ERR_UNSUPPORTED;
+  return by_hidden(d->hidden, [&](auto h) {   // the MFMA body (both towers of 64 rows per 512-thread workgroup)
+    constexpr int H = decltype(h)::value;
+    return launch_rows<policy_logits_mailbox_mfma_kernel<H>>(512, alds_bytes<H>(), n, stream, *d, params, params_t, norm_mean,
+                                                             norm_var, n, mb);
+  });
 }
 
 int ia_policy_evaluate(const ia_policy_desc* d, const float* params, const float* params_t, const float* norm_mean,
                        const float* norm_var, const float* obs, const float* actions, int n, float* logp,
                        float* values, float* entropy, void* stream) {
   if (!pol_ok(d) || n <= 0) return IA_ERR_ARG;
-  int rc;
-  if (d->hidden == 32 && (actions != nullptr || logp == nullptr)) {
-    static bool attr = false;   // the MFMA layer chain of the rollout step, given actions instead of sampling
-    const size_t bytes = ALds<32>::total * sizeof(float);
-    if (!attr) { if ((rc = set_lds(policy_act_mfma_kernel<32, true>, bytes))) return rc; attr = true; }
-    hipLaunchKernelGGL((policy_act_mfma_kernel<32, true>), dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream, *d,
-                       params, params_t, norm_mean, norm_var, obs, n, actions, (const float*)nullptr,
-                       (const float*)nullptr, (float*)nullptr, entropy, values, logp);
-  } else if (d->hidden == 64 && (actions != nullptr || logp == nullptr)) {
-    static bool attr = false;
-    const size_t bytes = ALds<64>::total * sizeof(float);
-    if (!attr) { if ((rc = set_lds(policy_act_mfma_kernel<64, true>, bytes))) return rc; attr = true; }
-    hipLaunchKernelGGL((policy_act_mfma_kernel<64, true>), dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream, *d,
-                       params, params_t, norm_mean, norm_var, obs, n, actions, (const float*)nullptr,
-                       (const float*)nullptr, (float*)nullptr, entropy, values, logp);
-  } else if (d->hidden == 32) {
-    if ((rc = set_lds(policy_eval_kernel<32>, lds_bytes<32>()))) return rc;
-    hipLaunchKernelGGL(policy_eval_kernel<32>, dim3(cdiv(n, ROWS)), dim3(ROWS), lds_bytes<32>(),
-                       (hipStream_t)stream, *d, params, params_t, norm_mean, norm_var, obs, actions, n, logp, values,
-                       entropy);
-  } else {
-    if ((rc = set_lds(policy_eval_kernel<64>, lds_bytes<64>()))) return rc;
-    hipLaunchKernelGGL(policy_eval_kernel<64>, dim3(cdiv(n, ROWS)), dim3(ROWS), lds_bytes<64>(),
-                       (hipStream_t)stream, *d, params, params_t, norm_mean, norm_var, obs, actions, n, logp, values,
-                       entropy);
-  }
-  IA_CHECK_LAUNCH();
-  return IA_OK;
+  return by_hidden(d->hidden, [&](auto h) {
+    constexpr int H = decltype(h)::value;
+    if (actions != nullptr || logp == nullptr)   // the MFMA layer chain of the rollout step, given actions instead of sampling
+      return launch_rows<policy_act_mfma_kernel<H, true>>(512, alds_bytes<H>(), n, stream, *d, params, params_t, norm_mean,
+                                                          norm_var, obs, n, actions, (const float*)nullptr,
+                                                          (const float*)nullptr, (float*)nullptr, entropy, values, logp);
+    return launch_rows<policy_eval_kernel<H>>(ROWS, lds_bytes<H>(), n, stream, *d, params, params_t, norm_mean, norm_var, obs,
+                                              actions, n, logp, values, entropy);   // a thread per row
+  });
 }
 
 int ia_policy_logits(const ia_policy_desc* d, const float* params, const float* params_t, const float* norm_mean,
                      const float* norm_var, const float* obs, int n, float* logits, float* values, void* stream) {
   if (!pol_ok(d) || n <= 0 || !logits) return IA_ERR_ARG;
-  int rc;
-  {   // the MFMA body: the same arithmetic as the mailbox kernel's steps
-    if (d->hidden == 32) {
-      const size_t bytes = ALds<32>::total * sizeof(float);
-      if ((rc = set_lds(policy_logits_mfma_kernel<32>, bytes))) return rc;
-      hipLaunchKernelGGL(policy_logits_mfma_kernel<32>, dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream, *d, params,
-                         params_t, norm_mean, norm_var, obs, n, logits, values);
-    } else {
-      const size_t bytes = ALds<64>::total * sizeof(float);
-      if ((rc = set_lds(policy_logits_mfma_kernel<64>, bytes))) return rc;
-      hipLaunchKernelGGL(policy_logits_mfma_kernel<64>, dim3(cdiv(n, ROWS)), dim3(512), bytes, (hipStream_t)stream, *d, params,
-                         params_t, norm_mean, norm_var, obs, n, logits, values);
-    }
-    IA_CHECK_LAUNCH();
-    return IA_OK;
-  }
-  return IA_ERR_UNSUPPORTED;
+  return by_hidden(d->hidden, [&](auto h) {   // the MFMA body: the same arithmetic as the mailbox kernel's steps
+    constexpr int H = decltype(h)::value;
+    return launch_rows<policy_logits_mfma_kernel<H>>(512, alds_bytes<H>(), n, stream, *d, params, params_t, norm_mean,
+                                                     norm_var, obs, n, logits, values);
+  });
 }
 
 int ia_gae(const float* rewards, const float* values, const float* episode_starts, const float* last_values,
@@ -6049,8 +6042,7 @@ int64_t ia_ppo_ws_floats(const ia_policy_desc* d, int batch, int64_t gather_rows
   if (!pol_ok(d) || batch <= 0 || gather_rows < batch) return IA_ERR_ARG;
   const int P = pol_offsets(d->obs_dim, d->act_dim, d->hidden, d->discrete).total;
   // (64-wide towers: the word exchange, laid out for 32-row blocks where they apply -- twice the slabs)
-  const int r64 = epoch_ll_row_blocks(cdiv(batch, ROWS), P), r32 = epoch_ll_row_blocks(cdiv(batch, 32), P);
-  const int64_t ll = d->hidden == 64 ? 2 * epoch_ll_words(r32 <= 32 ? r32 : r64, P) : 0;
+  const int64_t ll = d->hidden == 64 ? 2 * epoch_ll_words(epoch_ll_blocks(batch, P, 32).n, P) : 0;
   return ppo_ws_plain_floats(d, batch, gather_rows) + ll;
 }
 
@@ -6058,6 +6050,14 @@ int64_t ia_ppo_ws_floats(const ia_policy_desc* d, int batch, int64_t gather_rows
 
 namespace {
 
+bool g_epoch_split = false;  // tuning/debug: two launches per minibatch for 64-wide towers too
+bool g_epoch_whole = false;  // tuning/debug: the one-launch epoch with whole row-block workgroups (8 waves, both towers)
+bool g_epoch_barriers = false;   // tuning/debug: the one-tower epoch kernel with grid barriers instead of the word exchange
+bool g_epoch_chain2 = true;      // the word-exchange epoch kernel with round 5's transposed register-resident chain (observation
+                                 // widths <= 32); false: round 4's gradient body everywhere
+bool g_epoch_rows32 = true;      // round 6: that kernel on 32-row blocks where they fit (false: 64-row blocks, eight waves, everywhere)
+bool g_epoch_quarters = true;    // round 6: ... with eight waves per 32-row block (two row groups x four feature quarters)
+long long* g_epoch_dbg = nullptr;  // measurement: phase ticks of workgroup 0 of ppo_epoch_persistent_kernel
 long long* g_tstamp = nullptr;  // debug: device buffer of >= 16 clocks (ia_ppo_debug_timing)
 
 struct Gathered {  // contiguous (permuted-order) copies of the minibatch rows, inside ws
@@ -6076,6 +6076,7 @@ inline Gathered gathered_region(const ia_policy_desc* d, float* ws, int max_batc
   return g;
 }
 
+// What every PPO entry is given, in the entries' own order (`make_args`) ...
 struct PpoArgs {
   const ia_policy_desc* d;
   float *params, *params_t, *norm_mean, *norm_var;
@@ -6090,6 +6091,23 @@ struct PpoArgs {
   hipStream_t st;
   const float* advstat = nullptr;   // {advantage mean, std} of this minibatch (null: ws[0..1], left by the previous launch)
 };
+PpoArgs make_args(const ia_policy_desc* d, float* params, float* params_t, float* norm_mean, float* norm_var,
+                  int32_t* norm_count, int update_norm, const float* obs, const float* actions, const float* old_logp,
+                  const float* advantages, const float* returns, int T, int n_envs, int normalize_adv, float clip_range,
+                  float ent_coef, float vf_coef, float max_grad_norm, float* exp_avg, float* exp_avg_sq, double beta1,
+                  double beta2, float adam_eps, float* ws, void* stream) {
+  return PpoArgs{d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp, advantages,
+                 returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, max_grad_norm, exp_avg, exp_avg_sq,
+                 (float)beta1, (float)beta2, adam_eps, ws, (hipStream_t)stream};
+}
+// ... and what the whole-epoch and whole-update entries add: the minibatch sequence and Adam's schedule (in double)
+struct PpoSchedule {
+  const int64_t* perm;
+  int n_epochs, batch_size;
+  double lr, beta1, beta2;
+  int64_t adam_steps_done;
+  float* stats;
+};
 
 int launch_gather(const PpoArgs& a, const int64_t* perm, long long rows, const Gathered& g,
                   unsigned long long* zero_words = nullptr, long long n_zero = 0, unsigned* zero_ctl = nullptr) {
@@ -6102,7 +6120,7 @@ int launch_gather(const PpoArgs& a, const int64_t* perm, long long rows, const G
   return IA_OK;
 }
 
-// view of `a` whose row 0 is row `start` of the gathered arrays (kernels then run with idx == null)
+// view of `a` whose row 0 is row `start` of the gathered arrays (the kernels below run on such rows, without an index)
 PpoArgs at_rows(const PpoArgs& a, const Gathered& g, long long start) {
   const int aw = a.d->discrete ? 1 : a.d->act_dim;
   PpoArgs v = a;
@@ -6114,82 +6132,448 @@ PpoArgs at_rows(const PpoArgs& a, const Gathered& g, long long start) {
   return v;
 }
 
-int launch_prepare(const PpoArgs& a, const int64_t* idx, int batch) {
-  static bool attr = false;
+int launch_prepare(const PpoArgs& a, int batch) {
+  static LaunchSlot slot;
   const size_t bytes = PREP_LDS_FLOATS * sizeof(float);
-  if (!attr) { int rc = set_lds(ppo_prepare_kernel, bytes); if (rc) return rc; attr = true; }
+  if (int rc = ensure_lds(slot, ppo_prepare_kernel, bytes)) return rc;
   const PolOff o = pol_offsets(a.d->obs_dim, a.d->act_dim, a.d->hidden, a.d->discrete);
   const PpoWs w = ppo_ws(a.ws, cdiv(batch, ROWS), o.total);
-  hipLaunchKernelGGL(ppo_prepare_kernel, dim3(1), dim3(PREP_THREADS), bytes, a.st, *a.d, a.obs, a.advantages, idx,
-                     batch, a.T, a.n_envs, a.update_norm, a.norm_mean, a.norm_var, a.norm_count, w.advstat);
+  hipLaunchKernelGGL(ppo_prepare_kernel, dim3(1), dim3(PREP_THREADS), bytes, a.st, *a.d, a.obs, a.advantages,
+                     (const int64_t*)nullptr, batch, a.T, a.n_envs, a.update_norm, a.norm_mean, a.norm_var, a.norm_count,
+                     w.advstat);
   IA_CHECK_LAUNCH();
   return IA_OK;
 }
 
-
 template <int H>
-int launch_grad(const PpoArgs& a, const int64_t* idx, int batch) {
+int launch_grad_h(const PpoArgs& a, int batch) {
   const int nblk = cdiv(batch, ROWS);
   // matrix-core gradient kernel: H = 32 with the parameters copied into LDS, H = 64 reading its fragments from L2
   const int P4 = (pol_offsets(a.d->obs_dim, a.d->act_dim, H, a.d->discrete).total + 3) & ~3;
   const size_t mbytes = (GLds<H>::total + (H == 32 ? 2 * P4 : 0)) * sizeof(float);
-  static bool attr2 = false;
-  if (!attr2) { int rc = set_lds(ppo_grad_mfma_kernel<H>, 160 * 1024); if (rc) return rc; attr2 = true; }
+  static LaunchSlot slot;
+  if (int rc = ensure_lds(slot, ppo_grad_mfma_kernel<H>, 160 * 1024)) return rc;
   hipLaunchKernelGGL(ppo_grad_mfma_kernel<H>, dim3(nblk), dim3(512), mbytes, a.st, *a.d, a.params, a.params_t,
-                     a.norm_mean, a.norm_var, a.obs, a.actions, a.old_logp, a.advantages, a.returns, idx, batch, a.T,
-                     a.n_envs, a.normalize_adv, a.clip_range, a.ent_coef, a.vf_coef, a.ws, nblk, g_tstamp, a.advstat);
+                     a.norm_mean, a.norm_var, a.obs, a.actions, a.old_logp, a.advantages, a.returns,
+                     (const int64_t*)nullptr, batch, a.T, a.n_envs, a.normalize_adv, a.clip_range, a.ent_coef, a.vf_coef,
+                     a.ws, nblk, g_tstamp, a.advstat);
   IA_CHECK_LAUNCH();
   return IA_OK;
 }
+int launch_grad(const PpoArgs& a, int batch) {
+  return a.d->hidden == 32 ? launch_grad_h<32>(a, batch) : launch_grad_h<64>(a, batch);
+}
 
-// grad + apply for one minibatch whose statistics are already in ws; the apply kernel also
-// prepares minibatch `next_idx` (next_batch == 0: nothing follows). NOTE: both minibatches share
-// `ws`, whose slab region is sized by the LARGER batch; advstat sits at ws[0..7] for any size.
-int launch_minibatch_next(const PpoArgs& a, int batch, float step_size, float bc2_sqrt, float* stats,
-                          const PpoArgs& nxt, int next_batch);
-
-// reduce + clip + Adam (+ the next minibatch's statistics: in an extra workgroup when `stats_block`, else behind Adam)
+// reduce + clip + Adam of one minibatch whose gradient slabs are in ws (`nobs`, `nadv`: passed through to the kernel, which
+// prepares no next minibatch here)
 int launch_apply_split(const PpoArgs& a, int batch, float step_size, float bc2_sqrt, float* stats, const float* nobs,
-                       const float* nadv, const int64_t* next_idx, int next_batch, int stats_block) {
-  static bool attr = false;
+                       const float* nadv) {
+  static LaunchSlot slot;
   const size_t bytes = PREP_LDS_FLOATS * sizeof(float);
-  if (!attr) { int rc = set_lds(ppo_apply_split_kernel, bytes); if (rc) return rc; attr = true; }
+  if (int rc = ensure_lds(slot, ppo_apply_split_kernel, bytes)) return rc;
   const int nblk = cdiv(batch, ROWS);
   const int total = pol_offsets(a.d->obs_dim, a.d->act_dim, a.d->hidden, a.d->discrete).total;
   const int G = std::max(1, std::min(std::min(nblk, 16), cdiv(total, PREP_THREADS)));
-  hipLaunchKernelGGL(ppo_apply_split_kernel, dim3(G + (stats_block ? 1 : 0)), dim3(PREP_THREADS), bytes, a.st, *a.d,
-                     a.params, a.params_t, a.exp_avg, a.exp_avg_sq, a.ws, nblk, batch, a.max_grad_norm, a.ent_coef,
-                     a.vf_coef, a.beta1, a.beta2, a.adam_eps, step_size, bc2_sqrt, stats, nobs, nadv, next_idx, next_batch,
-                     a.T, a.n_envs, a.update_norm, a.norm_mean, a.norm_var, a.norm_count, G, stats_block);
+  hipLaunchKernelGGL(ppo_apply_split_kernel, dim3(G), dim3(PREP_THREADS), bytes, a.st, *a.d, a.params, a.params_t,
+                     a.exp_avg, a.exp_avg_sq, a.ws, nblk, batch, a.max_grad_norm, a.ent_coef, a.vf_coef, a.beta1, a.beta2,
+                     a.adam_eps, step_size, bc2_sqrt, stats, nobs, nadv, (const int64_t*)nullptr, 0, a.T, a.n_envs,
+                     a.update_norm, a.norm_mean, a.norm_var, a.norm_count, G, 0);
   IA_CHECK_LAUNCH();
   return IA_OK;
 }
 
-int launch_minibatch(const PpoArgs& a, const int64_t* idx, int batch, float step_size, float bc2_sqrt, float* stats,
-                     const int64_t* next_idx, int next_batch) {
-  int rc = a.d->hidden == 32 ? launch_grad<32>(a, idx, batch) : launch_grad<64>(a, idx, batch);
-  if (rc) return rc;
-  return launch_apply_split(a, batch, step_size, bc2_sqrt, stats, a.obs, a.advantages, next_idx, next_batch, 0);
-}
-
-// contiguous-rows form: `a` = this minibatch's rows, `nxt` = the next minibatch's rows (for its statistics)
-int launch_minibatch_next(const PpoArgs& a, int batch, float step_size, float bc2_sqrt, float* stats,
-                          const PpoArgs& nxt, int next_batch) {
-  int rc = a.d->hidden == 32 ? launch_grad<32>(a, nullptr, batch) : launch_grad<64>(a, nullptr, batch);
-  if (rc) return rc;
-  return launch_apply_split(a, batch, step_size, bc2_sqrt, stats, nxt.obs, nxt.advantages, nullptr, next_batch,
-                            next_batch > 0 ? 1 : 0);
-}
-
 int launch_apply_phase(const PpoArgs& a, int batch, float step_size, float bc2_sqrt, float* stats, int phases) {
-  static bool attr = false;
+  static LaunchSlot slot;
   const size_t bytes = PREP_LDS_FLOATS * sizeof(float);
-  if (!attr) { int rc = set_lds(ppo_apply_kernel, bytes); if (rc) return rc; attr = true; }
+  if (int rc = ensure_lds(slot, ppo_apply_kernel, bytes)) return rc;
   hipLaunchKernelGGL(ppo_apply_kernel, dim3(1), dim3(PREP_THREADS), bytes, a.st, *a.d, a.params, a.params_t, a.exp_avg,
                      a.exp_avg_sq, a.ws, cdiv(batch, ROWS), batch, a.max_grad_norm, a.ent_coef, a.vf_coef, a.beta1,
                      a.beta2, a.adam_eps, step_size, bc2_sqrt, stats, a.obs, a.advantages, nullptr, 0, a.T, a.n_envs, 0,
                      a.norm_mean, a.norm_var, a.norm_count, phases);
   IA_CHECK_LAUNCH();
+  return IA_OK;
+}
+
+// gather + statistics of ONE minibatch (rows `idx`) into ws; -> the view the gradient kernel then runs on
+int gather_and_prepare(const PpoArgs& a, const int64_t* idx, int batch, PpoArgs* v) {
+  const Gathered g = gathered_region(a.d, a.ws, batch, batch);
+  if (int rc = launch_gather(a, idx, batch, g)) return rc;
+  *v = at_rows(a, g, 0);
+  return launch_prepare(*v, batch);
+}
+
+// ---- which epoch form runs where (the table in DESIGN 4.2) -----------------------------------------------------------
+enum class EpochForm {
+  TwoLaunches,    // gradient + apply kernel per minibatch (32-wide towers; 64-wide ones that fit nothing below)
+  BarrierWhole,   // ppo_epoch_persistent_kernel<64>: whole row-block workgroups, grid barriers
+  BarrierSplit,   // ppo_epoch_persistent_kernel<64, true>: one tower per workgroup, grid barriers
+  Ll,             // ppo_epoch_ll_kernel: one tower per workgroup, word exchange
+  Ll2             // ppo_epoch_ll2_kernel: ... with the transposed register-resident chain
+};
+struct EpochSwitches {   // `ia_ppo_epoch_split`'s tuning switches, and whether `ia_ppo_debug_timing` has set a buffer
+  bool split, whole, barriers, chain2, rows32, quarters, timing;
+};
+struct EpochPlan {
+  EpochForm form;
+  int kernel;           // Ll, Ll2: index into kEpochLlKernels (`epoch_ll_index`, `epoch_ll2_index`)
+  int grid, threads;
+  size_t lds;           // dynamic LDS bytes of a launch
+  int ll_blocks;        // Ll, Ll2: row blocks the word areas are laid out for (0: no word areas) ...
+  int64_t ll_offset;    // ... and where they start in ws (floats)
+};
+
+constexpr size_t EPOCH_SPLIT_LDS = 160 * 1024 - 1024;   // dynamic LDS the one-tower kernel may ask for (it has static LDS too)
+constexpr size_t EPOCH_LL_LDS = 160 * 1024 - 2048;
+
+using EpochLlKernel = decltype(&ppo_epoch_ll2_kernel<1, 8, 64>);
+const EpochLlKernel kEpochLlKernels[9] = {
+    ppo_epoch_ll2_kernel<1, 8, 64>, ppo_epoch_ll2_kernel<2, 8, 64>,   // 64-row blocks: eight waves (feature halves), two per SIMD
+    ppo_epoch_ll2_kernel<1, 4, 32>, ppo_epoch_ll2_kernel<2, 4, 32>,   // round 6: 32-row blocks, feature halves
+    ppo_epoch_ll2_kernel<1, 8, 32>, ppo_epoch_ll2_kernel<2, 8, 32>,   // round 6: 32-row blocks, feature quarters (two waves per SIMD)
+    ppo_epoch_ll_kernel<64, 20>, ppo_epoch_ll_kernel<64, 24>, ppo_epoch_ll_kernel<64, 33>};
+inline int epoch_ll2_index(int obs_dim, bool rows32, int waves) {
+  return (obs_dim <= 16 ? 0 : 1) + (rows32 ? (waves == 8 ? 4 : 2) : 0);
+}
+inline int epoch_ll_index(int tlen) { return tlen <= 20 * 256 ? 6 : (tlen <= 24 * 256 ? 7 : 8); }   // NLL = 20 / 24 / 33
+LaunchSlot g_epoch_ll_slots[9];
+
+// The epoch form for minibatches of `b0` rows (the sequence's first, i.e. largest) out of `total` gathered rows on a
+// device of `cus` compute units. Pure: no HIP call, no launch.
+EpochPlan plan_epoch(const ia_policy_desc* d, int b0, long long total, int cus, const EpochSwitches& sw) {
+  EpochPlan p{EpochForm::TwoLaunches, 0, 0, 0, 0, 0, 0};
+  if (d->hidden != 64 || sw.split || sw.timing) return p;
+  const PolOff po = pol_offsets(d->obs_dim, d->act_dim, d->hidden, d->discrete);
+  const int P = po.total, nrb = cdiv(b0, ROWS), aw = d->discrete ? 1 : d->act_dim;
+  // one tower per workgroup (two workgroups of four waves per row block, the tower's parameters resident in LDS) when
+  // both fit: 2 nrb workgroups co-resident, chunks of <= 4 x 256 parameters, the larger tower's images beside its tiles
+  const int tlen = 64 * d->obs_dim + 64 + 64 * 64 + 64, lenB = std::max(po.cW - po.aW, P - po.cW) + 3;
+  const size_t sbytes = (size_t)(((GLds<64, 1>::total + 3) & ~3) + 2 * tlen + 4 * d->obs_dim + 128 + lenB + MAXA) * sizeof(float);
+  const bool towers_fit = !sw.whole && 2 * nrb <= cus && 2 * nrb <= 64;
+  // the word-exchange form of the one-tower kernel (no grid barriers); its word areas sit behind everything else in ws.
+  // Small minibatches (down to ONE row block: SB3's default batch_size = 64): the launch has as many workgroups as it takes
+  // for chunks of <= 1 024 parameters -- those beyond the row blocks run no gradient phase, they sum, clip and step their
+  // chunk (`epoch_ll_row_blocks`)
+  const int nrb_l = epoch_ll_row_blocks(nrb, P);
+  if (towers_fit && !sw.barriers && sbytes + 16 <= EPOCH_LL_LDS && nrb_l <= 32 && 2 * nrb_l <= cus) {
+    // round 5's gradient phase (transposed register-resident chain, images with ds_read_b128 fragments) ...
+    const bool chain2 = sw.chain2 && d->obs_dim <= 32;
+    // ... round 6: on 32-ROW blocks (twice the workgroups, half the chain and half the weight-gradient tiles per compute
+    // unit) where its 2 x ceil(b / 32) workgroups and slabs fit the exchange's limits (minibatches <= 1 024 rows)
+    const LlBlocks lb = epoch_ll_blocks(b0, P, chain2 && sw.rows32 ? std::min(32, cus / 2) : 0);
+    p.ll_blocks = lb.n;
+    p.ll_offset = ppo_ws_plain_floats(d, b0, total);
+    const size_t l2bytes = (size_t)(d->obs_dim <= 16 ? T64Geo<1>(d->obs_dim, aw).total : T64Geo<2>(d->obs_dim, aw).total) *
+                               sizeof(float) + 16;
+    if (chain2 && l2bytes <= EPOCH_LL_LDS) {
+      const int waves = lb.rows32 && !sw.quarters ? 4 : 8;
+      p.form = EpochForm::Ll2;
+      p.kernel = epoch_ll2_index(d->obs_dim, lb.rows32, waves);
+      p.grid = 2 * lb.n; p.threads = 64 * waves; p.lds = l2bytes;
+    } else {
+      p.form = EpochForm::Ll;
+      p.kernel = epoch_ll_index(tlen);
+      p.grid = 2 * nrb_l; p.threads = 256; p.lds = sbytes + 16;
+    }
+    return p;
+  }
+  // grid barriers: one launch per (<= 64 minibatches of the) epoch when every gradient workgroup can be resident at once
+  const bool split = towers_fit && sbytes <= EPOCH_SPLIT_LDS && cdiv(P, 2 * nrb) <= 4 * 256;
+  const int nwg = split ? 2 * nrb : nrb;
+  if (nwg <= cus && nwg <= 64 && cdiv(P, nwg) <= 4 * (split ? 256 : 512)) {
+    p.form = split ? EpochForm::BarrierSplit : EpochForm::BarrierWhole;
+    p.grid = nwg; p.threads = split ? 256 : 512; p.lds = split ? sbytes : GLds<64>::total * sizeof(float);
+  }
+  return p;
+}
+
+// One full PPO epoch (SB3 PPO.train inner loop over RolloutBuffer.get): `perm` is the host-drawn
+// np.random.permutation(T*n_envs) already resident on the device; minibatches are consecutive
+// slices of it (the last one may be short). Adam's bias corrections are formed in double per step.
+// Launches: 1 prepare + 2 per minibatch.
+// `n_epochs` consecutive epochs as ONE sequence of minibatches (`perm` = the epochs' permutations back to back): valid when
+// the rollout divides into whole minibatches (no minibatch then straddles two epochs and every minibatch is the one the
+// per-epoch call makes); gather, statistics and the epoch kernels run over n_epochs x T x n_envs rows.
+int ppo_epochs_impl(const PpoArgs& a, const PpoSchedule& s) {
+  const ia_policy_desc* d = a.d;
+  if (!pol_ok(d) || s.batch_size <= 0 || s.n_epochs < 1) return IA_ERR_ARG;
+  if (s.n_epochs > 1 && ((long long)a.T * a.n_envs) % s.batch_size != 0) return IA_ERR_UNSUPPORTED;
+  const long long total = (long long)a.T * a.n_envs * s.n_epochs;
+  auto size_at = [&](long long start) { return (int)((total - start) < s.batch_size ? (total - start) : s.batch_size); };
+  const Gathered g = gathered_region(d, a.ws, size_at(0), total);
+  const int cus = device_cus();
+  if (cus <= 0) return IA_ERR_ARG;
+  const EpochPlan p = plan_epoch(d, size_at(0), total, cus,
+                                 EpochSwitches{g_epoch_split, g_epoch_whole, g_epoch_barriers, g_epoch_chain2, g_epoch_rows32,
+                                               g_epoch_quarters, g_tstamp != nullptr});
+  // the word-exchange forms have their areas and control words (4, 5, 6: counter, error word, ticket) cleared by the gather
+  const bool ll = p.ll_blocks > 0;
+  const int P = pol_offsets(d->obs_dim, d->act_dim, d->hidden, d->discrete).total;
+  EpochLl el{};
+  el.base = ll ? reinterpret_cast<unsigned long long*>(a.ws + p.ll_offset) : nullptr;
+  int rc = launch_gather(a, s.perm, total, g, el.base, ll ? epoch_ll_words(p.ll_blocks, P) : 0,
+                         ll ? reinterpret_cast<unsigned*>(a.ws) + 4 : nullptr);
+  if (rc) return rc;
+  // statistics of every minibatch of the epoch, one launch ahead of the chain (ppo_epoch_stats_kernel)
+  const int n_mb = (int)((total + s.batch_size - 1) / s.batch_size);
+  float* seq = g.ret + total;                       // [n_mb][EPS_SEQ]
+  float* part = seq + (long long)n_mb * EPS_SEQ;    // [n_mb][EPS_PART]
+  {
+    static LaunchSlot slot;
+    const size_t bytes = PREP_LDS_FLOATS * sizeof(float);
+    if ((rc = ensure_lds(slot, ppo_epoch_stats_kernel, bytes))) return rc;
+    if (!ll && hipMemsetAsync(a.ws + 6, 0, sizeof(unsigned), a.st) != hipSuccess) return IA_ERR_ARG;   // its ticket (ws is not pre-zeroed)
+    hipLaunchKernelGGL(ppo_epoch_stats_kernel, dim3(n_mb), dim3(PREP_THREADS), bytes, a.st, *d, g.obs, g.adv, total,
+                       s.batch_size, a.update_norm, a.norm_mean, a.norm_var, a.norm_count, seq, part,
+                       reinterpret_cast<unsigned*>(a.ws) + 6);
+    IA_CHECK_LAUNCH();
+  }
+  const bool snap = d->has_norm && a.update_norm;
+  int64_t step = s.adam_steps_done;
+  if (p.form == EpochForm::TwoLaunches) {
+    int mb = 0;
+    for (long long start = 0; start < total; start += s.batch_size, ++mb) {
+      const int b = size_at(start);
+      const AdamScalars as = adam_scalars(++step, s.lr, s.beta1, s.beta2);
+      PpoArgs v = at_rows(a, g, start);
+      float* sq = seq + (long long)mb * EPS_SEQ;
+      v.advstat = sq;
+      if (snap) { v.norm_mean = sq + 8; v.norm_var = sq + 8 + MAXD; }
+      if ((rc = launch_grad(v, b))) return rc;
+      rc = launch_apply_split(v, b, as.step_size, as.bc2_sqrt, s.stats ? s.stats + mb * 8 : nullptr, nullptr, nullptr);
+      if (rc) return rc;
+    }
+    return IA_OK;
+  }
+  // one launch per <= EpochSteps::MAX minibatches of the sequence
+  using BarrierKernel = decltype(&ppo_epoch_persistent_kernel<64>);
+  static const BarrierKernel barrier_kernels[2] = {ppo_epoch_persistent_kernel<64>, ppo_epoch_persistent_kernel<64, true>};
+  static LaunchSlot barrier_slots[2];
+  const bool barrier = p.form == EpochForm::BarrierWhole || p.form == EpochForm::BarrierSplit;
+  const int bk = p.form == EpochForm::BarrierSplit ? 1 : 0;
+  rc = barrier ? ensure_lds(barrier_slots[bk], barrier_kernels[bk], bk ? EPOCH_SPLIT_LDS : p.lds)
+               : ensure_lds(g_epoch_ll_slots[p.kernel], kEpochLlKernels[p.kernel], EPOCH_LL_LDS);
+  if (rc) return rc;
+  if (barrier && hipMemsetAsync(a.ws + 4, 0, 2 * sizeof(unsigned), a.st) != hipSuccess) return IA_ERR_ARG;   // barrier counter, error word
+  for (int first = 0; first < n_mb; first += EpochSteps::MAX) {
+    EpochSteps es{};
+    es.first = first;
+    es.n = std::min(EpochSteps::MAX, n_mb - first);
+    for (int k = 0; k < es.n; ++k) {
+      const AdamScalars as = adam_scalars(++step, s.lr, s.beta1, s.beta2);
+      es.step_size[k] = as.step_size;
+      es.bc2_sqrt[k] = as.bc2_sqrt;
+    }
+    // (`word_areas`: the word-exchange kernels' one extra argument)
+    auto launch = [&](auto kern, auto... word_areas) {
+      hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.threads), p.lds, a.st, *d, a.params, a.params_t, a.exp_avg, a.exp_avg_sq,
+                         a.norm_mean, a.norm_var, g.obs, g.act, g.logp, g.adv, g.ret, total, s.batch_size, a.T, a.n_envs,
+                         a.normalize_adv, a.clip_range, a.ent_coef, a.vf_coef, a.max_grad_norm, a.beta1, a.beta2, a.adam_eps,
+                         a.ws, word_areas..., seq, snap ? 1 : 0, s.stats, es, g_epoch_dbg);
+    };
+    if (barrier) {
+      if (first > 0 && hipMemsetAsync(a.ws + 4, 0, sizeof(unsigned), a.st) != hipSuccess) return IA_ERR_ARG;
+      launch(barrier_kernels[bk]);
+    } else {
+      el.seq0 = (unsigned)(s.adam_steps_done + first + 1);   // (the areas were cleared, like the error word, by the gather launch)
+      launch(kEpochLlKernels[p.kernel], el);
+    }
+    IA_CHECK_LAUNCH();
+  }
+  return IA_OK;
+}
+
+// LDS of a gradient block: minibatch tiles, both parameter copies, the staged next minibatch, the transpose map
+inline size_t upd_grad_lds_bytes(int P4, int aw) {
+  return 16 /* base rounded up to 16 bytes */ + (CLds::total + (size_t)P4 + upd_pt4(P4) + UpdStage::total(aw)) * sizeof(float) +
+         P4 * sizeof(unsigned short);
+}
+
+// Workspace of ia_ppo_update in floats; 0 when the persistent kernel does not cover the shape
+// (the caller then runs ia_ppo_epoch per epoch).
+int64_t upd_ws_floats(const ia_policy_desc* d, int batch_size, int world) {
+  if (!pol_ok(d) || batch_size <= 0 || world < 1 || world > SHARD_WORLD_MAX) return IA_ERR_ARG;
+  const int P = pol_offsets(d->obs_dim, d->act_dim, d->hidden, d->discrete).total;
+  const int nblk = cdiv(batch_size, ROWS);
+  const int P4 = (P + 3) & ~3;
+  if (d->hidden != 32 || P > UPD_NPT_WIDE * 512 || upd_grad_lds_bytes(P4, d->discrete ? 1 : d->act_dim) > 160 * 1024 || nblk > UPD_NBLK_MAX ||
+      cdiv((long long)batch_size * world, UPD_SLICE) > UPD_SLICES_MAX)
+    return 0;
+  // (every gradient workgroup polls nblk x ceil((P4 + 8) / nblk) slab words with its parameters-per-thread x 512 lanes)
+  if (nblk > 1 && P4 + 8 + nblk - 1 > UPD_NPT_WIDE * 512) return 0;
+  return UPD_CTRL + 2 * UPD_MAX_STEPS + UPD_RING * UPD_RS + UPD_SD * 2 + UPD_SD * (int64_t)nblk * 8 +
+         4 * (int64_t)nblk * (P4 + 8) + 4 * (int64_t)(P4 + 8) + (int64_t)UPD_RING * UPD_SLICES_MAX * UPD_PRS;
+}
+
+bool g_upd_xcd_pack = false;   // opt-in (ia_ppo_update_xcd_pack): several gradient workgroups that fit one XCD packed there
+constexpr int HOST_TAB_SLOTS = 8;
+struct HostTab { float* buf = nullptr; hipEvent_t done; };
+HostTab g_host_tab[HOST_TAB_SLOTS];
+int g_host_tab_next = 0;
+int g_upd_assume_cus = 0;         // (ia_ppo_update_assume_cus) > 0: the update's residency tests count this many compute units
+bool g_upd_tower_split = false;   // (ia_ppo_update_tower_split) two gradient workgroups per row block, one per tower, where they fit
+int g_upd_slice_owner = 0;   // (ia_ppo_update_slice_owner) hop 1 of the tower-split form: 0 every gradient workgroup owns a slice,
+                             // 1 the value workgroups own a value and a policy slice each, the policy workgroups none
+
+// instantiations: {8, 9} parameters per thread x {production, phase clocks} x first-layer fragments for <= 32 / <= 64
+// observation columns (the narrow form keeps 16 registers less across the chain) x the gradient kept in LDS (`local`)
+using UpdKernel = decltype(&ppo_update_persistent_kernel<UPD_NPT, false, 8, false>);
+const UpdKernel kUpdKernels[32] = {
+    ppo_update_persistent_kernel<UPD_NPT, false, 8, false>,      ppo_update_persistent_kernel<UPD_NPT, false, 16, false>,
+    ppo_update_persistent_kernel<UPD_NPT, true, 8, false>,       ppo_update_persistent_kernel<UPD_NPT, true, 16, false>,
+    ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, false>, ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, false>,
+    ppo_update_persistent_kernel<UPD_NPT_WIDE, true, 8, false>,  ppo_update_persistent_kernel<UPD_NPT_WIDE, true, 16, false>,
+    ppo_update_persistent_kernel<UPD_NPT, false, 8, true>,       ppo_update_persistent_kernel<UPD_NPT, false, 16, true>,
+    ppo_update_persistent_kernel<UPD_NPT, true, 8, true>,        ppo_update_persistent_kernel<UPD_NPT, true, 16, true>,
+    ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, true>,  ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, true>,
+    ppo_update_persistent_kernel<UPD_NPT_WIDE, true, 8, true>,   ppo_update_persistent_kernel<UPD_NPT_WIDE, true, 16, true>,
+    // row-sharded data parallelism (no phase-clock build)
+    ppo_update_persistent_kernel<UPD_NPT, false, 8, false, true>,      ppo_update_persistent_kernel<UPD_NPT, false, 16, false, true>,
+    ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, false, true>, ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, false, true>,
+    ppo_update_persistent_kernel<UPD_NPT, false, 8, true, true>,       ppo_update_persistent_kernel<UPD_NPT, false, 16, true, true>,
+    ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, true, true>,  ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, true, true>,
+    // one gradient workgroup, minibatches of <= 16 rows (the tuned AIRL file): six of the eight waves skip the layer chain,
+    // each tower's one wave has a SIMD to itself (`small`; no phase-clock build either)
+    ppo_update_persistent_kernel<UPD_NPT, false, 8, true, false, true>,       ppo_update_persistent_kernel<UPD_NPT, false, 16, true, false, true>,
+    ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, true, false, true>,  ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, true, false, true>,
+    ppo_update_persistent_kernel<UPD_NPT, false, 8, true, true, true>,        ppo_update_persistent_kernel<UPD_NPT, false, 16, true, true, true>,
+    ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, true, true, true>,   ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, true, true, true>};
+inline int upd_kernel_index(bool small, bool shard, bool local, bool wide, bool timing, bool ks16) {
+  if (small) return 24 + shard * 4 + wide * 2 + ks16;
+  if (shard) return 16 + local * 4 + wide * 2 + ks16;
+  return local * 8 + wide * 4 + timing * 2 + ks16;
+}
+LaunchSlot g_upd_slots[32];
+
+// One tower per gradient workgroup (`ppo_update_split_kernel`); [8 ..]: the same with hop 1's slices by tower on the value
+// workgroups (`ia_ppo_update_slice_owner(1)`). Its own LDS-attribute and occupancy slots.
+const UpdKernel kUpdSplitKernels[16] = {
+    ppo_update_split_kernel<UPD_NPT, false, 8>,      ppo_update_split_kernel<UPD_NPT, false, 16>,
+    ppo_update_split_kernel<UPD_NPT, true, 8>,       ppo_update_split_kernel<UPD_NPT, true, 16>,
+    ppo_update_split_kernel<UPD_NPT_WIDE, false, 8>, ppo_update_split_kernel<UPD_NPT_WIDE, false, 16>,
+    ppo_update_split_kernel<UPD_NPT_WIDE, true, 8>,  ppo_update_split_kernel<UPD_NPT_WIDE, true, 16>,
+    ppo_update_owner_kernel<UPD_NPT, false, 8>,      ppo_update_owner_kernel<UPD_NPT, false, 16>,
+    ppo_update_owner_kernel<UPD_NPT, true, 8>,       ppo_update_owner_kernel<UPD_NPT, true, 16>,
+    ppo_update_owner_kernel<UPD_NPT_WIDE, false, 8>, ppo_update_owner_kernel<UPD_NPT_WIDE, false, 16>,
+    ppo_update_owner_kernel<UPD_NPT_WIDE, true, 8>,  ppo_update_owner_kernel<UPD_NPT_WIDE, true, 16>};
+inline int upd_split_index(bool by_tower, bool wide, bool timing, bool ks16) {
+  return by_tower * 8 + wide * 4 + timing * 2 + ks16;
+}
+LaunchSlot g_upd_split_slots[16];
+
+// A whole PPO.train: n_epochs passes over consecutive minibatches of perm[e][T*n_envs] (SB3
+// RolloutBuffer.get order), in ONE persistent launch per <= UPD_MAX_STEPS optimiser steps.
+// stats: [n_epochs * n_minibatches][8] or NULL. ws must be zero-initialised once by the caller;
+// word 8 of it is a sticky error flag (non-zero: a grid wait timed out, results invalid).
+// `shard` (ia_ppo_update_sharded): `batch_size` is the rank's rows per minibatch, `n_envs` the global tile's width; the
+// schedule (minibatch size world x batch_size, statistics slices) is the global one, the gradient workgroups are the rank's.
+int ppo_update_launch(const PpoArgs& a, const PpoSchedule& s, const ShardArgs* shard) {
+  const ia_policy_desc* d = a.d;
+  const int world = shard ? shard->world : 1;
+  if (!pol_ok(d) || s.batch_size <= 0 || s.n_epochs <= 0 || upd_ws_floats(d, s.batch_size, world) <= 0) return IA_ERR_ARG;
+  const long long total = (long long)a.T * a.n_envs;
+  const int batch_global = s.batch_size * world;
+  const int n_mb = cdiv(total, batch_global);
+  const int nblk = cdiv(s.batch_size, ROWS);
+  const PolOff po = pol_offsets(d->obs_dim, d->act_dim, 32, d->discrete);
+  const int P = po.total;
+  const int P4 = (P + 3) & ~3;
+  const size_t grad_bytes = upd_grad_lds_bytes(P4, d->discrete ? 1 : d->act_dim);
+  const size_t prep_bytes = (PREP_LDS_FLOATS + (size_t)cdiv(batch_global, ROWS) * ROWS) * sizeof(float);  // + row offsets
+  const size_t bytes = grad_bytes > prep_bytes ? grad_bytes : prep_bytes;
+  const bool wide = P > UPD_NPT * 512 || (nblk > 1 && P4 + 8 + nblk - 1 > UPD_NPT * 512);
+  const bool timing = g_tstamp != nullptr;
+  const bool ks16 = d->obs_dim > 32;
+  // one gradient workgroup whose parameter vector fits the consumed part of the staging area: the gradient stays in LDS
+  const bool local = nblk == 1 && P4 <= UpdStage::nxt;
+  const bool small = local && s.batch_size <= 16 && !timing;
+  const int vi_k = upd_kernel_index(small, shard != nullptr, local, wide, timing, ks16);
+  // One tower per gradient workgroup: several gradient workgroups of one process, switch on, and -- checked per launch
+  // below -- 2 nblk + 1 + 2 n_slices workgroups co-resident; otherwise the form above, unchanged.
+  const bool want_split = g_upd_tower_split && shard == nullptr && nblk >= 2;
+  // slices by tower: each of an owner's two passes polls nblk x ceil(set / nblk) words with its parameters-per-thread x 512
+  // lanes (sets: the value elements; the policy elements + 5 loss-statistic words); a pass that does not fit -> ownership 0
+  const int n_pol = po.vW1 + (po.cW - po.aW) + 5, n_val = P - (n_pol - 5);
+  const int own_lanes = (wide ? UPD_NPT_WIDE : UPD_NPT) * 512;
+  const bool by_tower = g_upd_slice_owner == 1 && nblk * cdiv(n_pol, nblk) <= own_lanes && nblk * cdiv(n_val, nblk) <= own_lanes;
+  const int vi_s = upd_split_index(by_tower, wide, timing, ks16);
+  const UpdKernel kernel = kUpdKernels[vi_k], split_kernel = kUpdSplitKernels[vi_s];
+  int rc = ensure_lds(g_upd_slots[vi_k], kernel, bytes);
+  if (rc) return rc;
+  const int dev_cus = device_cus();
+  if (dev_cus <= 0) return IA_ERR_ARG;
+  const int cus = g_upd_assume_cus > 0 ? g_upd_assume_cus : dev_cus;
+  const int steps_total = s.n_epochs * n_mb;
+  int64_t step = s.adam_steps_done;
+  for (int first = 0; first < steps_total; first += UPD_MAX_STEPS) {
+    UpdSched sch;
+    sch.n_steps = steps_total - first < UPD_MAX_STEPS ? steps_total - first : UPD_MAX_STEPS;
+    sch.first = first; sch.n_mb = n_mb; sch.batch_size = batch_global; sch.total = total;
+    // Adam's per-step scalars, staged through a small ring of pinned buffers (a slot is reused only after its copy has
+    // completed).
+    HostTab& ht = g_host_tab[g_host_tab_next];
+    g_host_tab_next = (g_host_tab_next + 1) % HOST_TAB_SLOTS;
+    if (ht.buf == nullptr) {
+      hipError_t e0 = hipHostMalloc(reinterpret_cast<void**>(&ht.buf), 2 * UPD_MAX_STEPS * sizeof(float), 0);
+      if (e0 != hipSuccess) return (int)e0;
+      e0 = hipEventCreateWithFlags(&ht.done, hipEventDisableTiming);
+      if (e0 != hipSuccess) return (int)e0;
+    } else {
+      hipError_t e0 = hipEventSynchronize(ht.done);
+      if (e0 != hipSuccess) return (int)e0;
+    }
+    for (int k = 0; k < sch.n_steps; ++k) {
+      const AdamScalars as = adam_scalars(++step, s.lr, s.beta1, s.beta2);
+      ht.buf[k] = as.step_size;
+      ht.buf[UPD_MAX_STEPS + k] = as.bc2_sqrt;
+    }
+    const UpdWs uw = upd_ws(a.ws, nblk, P);
+    hipError_t ec = hipMemcpyAsync(uw.tab, ht.buf, 2 * UPD_MAX_STEPS * sizeof(float), hipMemcpyHostToDevice, a.st);
+    if (ec != hipSuccess) return (int)ec;
+    ec = hipEventRecord(ht.done, a.st);
+    if (ec != hipSuccess) return (int)ec;
+    hipError_t e = hipMemsetAsync(a.ws, 0, 8 * sizeof(unsigned), a.st);  // published / second-level arrivals (error word stays)
+    if (e != hipSuccess) return (int)e;
+    e = hipMemsetAsync(a.ws + 16, 0, (UPD_CTRL - 16) * sizeof(unsigned), a.st);  // per-slicer progress, arrival counters
+    if (e != hipSuccess) return (int)e;
+    // packing onto one XCD only works while all workgroups fit its 32 CUs (each takes a whole CU's LDS)
+    // minibatches beyond UPD_SLICE rows: their statistics are cut into UPD_SLICE-row slices, one extra block
+    // each, merged in order by the statistics block. (One block needs 22 us for the gathered moments of a
+    // 1024-row minibatch -- as long as a whole gradient step, so the chain kept waiting 1-2 us per step for
+    // it; two slices + merge take ~14 us and the ring runs ahead again.)
+    const int n_slices = (batch_global > UPD_SLICE && total < (1ll << 31)) ? cdiv(batch_global, UPD_SLICE) : 0;
+    bool pack = g_upd_xcd_pack && nblk > 1 && nblk + 1 + n_slices <= 32;
+    int grid = (nblk + 1 + n_slices) * (pack ? 8 : 1);
+    UpdKernel launch_kernel = kernel;
+    if (want_split) {   // the same residency test for the wider grid; no room -> the two-tower form (and ITS test) below
+      if ((rc = ensure_lds(g_upd_split_slots[vi_s], split_kernel, bytes))) return rc;
+      const int split_grid = 2 * nblk + 1 + 2 * n_slices;   // (two workgroups per statistics slice: even / odd steps)
+      rc = fits_resident(g_upd_split_slots[vi_s], split_kernel, 512, bytes, split_grid, cus);
+      if (rc == IA_OK) {
+        launch_kernel = split_kernel;
+        grid = split_grid;
+        pack = false;   // (packing onto one XCD does not apply: twice the workgroups, and they are meant to spread)
+      } else if (rc != IA_ERR_UNSUPPORTED) {
+        return rc;
+      }
+    }
+    // The grid barriers inside need every workgroup resident at once. Not enough room -> IA_ERR_UNSUPPORTED, the caller
+    // runs ia_ppo_epoch (two launches per minibatch).
+    if (launch_kernel == kernel && (rc = fits_resident(g_upd_slots[vi_k], kernel, 512, bytes, pack ? grid / 8 : grid, cus)))
+      return rc;
+    ShardArgs sa;
+    if (shard) {
+      sa = *shard;
+      sa.seq_base = shard->seq_base + (unsigned)first;
+    } else {
+      memset(&sa, 0, sizeof(sa));
+    }
+    hipLaunchKernelGGL(launch_kernel, dim3(grid), dim3(512), bytes, a.st, *d, a.params, a.params_t, a.exp_avg,
+                       a.exp_avg_sq, a.norm_mean, a.norm_var, a.norm_count, a.update_norm, a.obs, a.actions, a.old_logp,
+                       a.advantages, a.returns, s.perm, a.T, a.n_envs, a.normalize_adv, a.clip_range, a.ent_coef, a.vf_coef,
+                       a.max_grad_norm, a.beta1, a.beta2, a.adam_eps, a.ws, nblk, n_slices, s.stats, sch, pack ? 1 : 0,
+                       g_tstamp, sa);
+    IA_CHECK_LAUNCH();
+  }
   return IA_OK;
 }
 
@@ -6205,16 +6589,13 @@ int ia_ppo_minibatch(const ia_policy_desc* d, float* params, float* params_t, fl
                      float beta2, float adam_eps, float step_size, float bc2_sqrt, float* ws, float* stats,
                      void* stream) {
   if (!pol_ok(d) || batch <= 0) return IA_ERR_ARG;
-  PpoArgs a{d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp, advantages,
-            returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, max_grad_norm, exp_avg, exp_avg_sq,
-            beta1, beta2, adam_eps, ws, (hipStream_t)stream};
-  const Gathered g = gathered_region(d, ws, batch, batch);
-  int rc = launch_gather(a, idx, batch, g);
-  if (rc) return rc;
-  const PpoArgs v = at_rows(a, g, 0);
-  rc = launch_prepare(v, nullptr, batch);
-  if (rc) return rc;
-  return launch_minibatch(v, nullptr, batch, step_size, bc2_sqrt, stats, nullptr, 0);
+  const PpoArgs a = make_args(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp,
+                              advantages, returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, max_grad_norm,
+                              exp_avg, exp_avg_sq, beta1, beta2, adam_eps, ws, stream);
+  PpoArgs v;
+  int rc = gather_and_prepare(a, idx, batch, &v);
+  if (rc || (rc = launch_grad(v, batch))) return rc;
+  return launch_apply_split(v, batch, step_size, bc2_sqrt, stats, v.obs, v.advantages);
 }
 
 // Data-parallel split of a minibatch step (one rank per GPU): `_grad` = statistics + forward/backward
@@ -6226,17 +6607,12 @@ int ia_ppo_minibatch_grad(const ia_policy_desc* d, float* params, float* params_
                           int batch, int T, int n_envs, int normalize_adv, float clip_range, float ent_coef,
                           float vf_coef, float* ws, void* stream) {
   if (!pol_ok(d) || batch <= 0) return IA_ERR_ARG;
-  PpoArgs a{d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp, advantages,
-            returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, 0.f, nullptr, nullptr, 0.f, 0.f, 0.f, ws,
-            (hipStream_t)stream};
-  const Gathered g = gathered_region(d, ws, batch, batch);
-  int rc = launch_gather(a, idx, batch, g);
-  if (rc) return rc;
-  const PpoArgs v = at_rows(a, g, 0);
-  rc = launch_prepare(v, nullptr, batch);
-  if (rc) return rc;
-  rc = d->hidden == 32 ? launch_grad<32>(v, nullptr, batch) : launch_grad<64>(v, nullptr, batch);
-  if (rc) return rc;
+  const PpoArgs a = make_args(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp,
+                              advantages, returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, 0.f, nullptr,
+                              nullptr, 0.f, 0.f, 0.f, ws, stream);
+  PpoArgs v;
+  int rc = gather_and_prepare(a, idx, batch, &v);
+  if (rc || (rc = launch_grad(v, batch))) return rc;
   return launch_apply_phase(v, batch, 0.f, 1.f, nullptr, 1);
 }
 
@@ -6274,211 +6650,11 @@ int ia_ppo_minibatch_apply(const ia_policy_desc* d, float* params, float* params
                            float beta2, float adam_eps, float step_size, float bc2_sqrt, float* ws, float* stats,
                            void* stream) {
   if (!pol_ok(d) || batch <= 0) return IA_ERR_ARG;
-  PpoArgs a{d, params, params_t, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
-            0.f, ent_coef, vf_coef, max_grad_norm, exp_avg, exp_avg_sq, beta1, beta2, adam_eps, ws,
-            (hipStream_t)stream};
+  const PpoArgs a = make_args(d, params, params_t, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              0, 0, 0, 0.f, ent_coef, vf_coef, max_grad_norm, exp_avg, exp_avg_sq, beta1, beta2, adam_eps,
+                              ws, stream);
   return launch_apply_phase(a, batch, step_size, bc2_sqrt, stats, 2);
 }
-
-// One full PPO epoch (SB3 PPO.train inner loop over RolloutBuffer.get): `perm` is the host-drawn
-// np.random.permutation(T*n_envs) already resident on the device; minibatches are consecutive
-// slices of it (the last one may be short). Adam's bias corrections are formed in double per step.
-// Launches: 1 prepare + 2 per minibatch.
-// `n_epochs` consecutive epochs as ONE sequence of minibatches (`perm` = the epochs' permutations back to back): valid when
-// the rollout divides into whole minibatches (no minibatch then straddles two epochs and every minibatch is the one the
-// per-epoch call makes); gather, statistics and the epoch kernels run over n_epochs x T x n_envs rows.
-static int ppo_epochs_impl(const ia_policy_desc* d, float* params, float* params_t, float* norm_mean, float* norm_var,
-                 int32_t* norm_count, int update_norm, const float* obs, const float* actions, const float* old_logp,
-                 const float* advantages, const float* returns, const int64_t* perm, int n_epochs, int T, int n_envs,
-                 int batch_size, int normalize_adv, float clip_range, float ent_coef, float vf_coef,
-                 float max_grad_norm, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2,
-                 float adam_eps, int64_t adam_steps_done, float* ws, float* stats, void* stream) {
-  if (!pol_ok(d) || batch_size <= 0 || n_epochs < 1) return IA_ERR_ARG;
-  if (n_epochs > 1 && ((long long)T * n_envs) % batch_size != 0) return IA_ERR_UNSUPPORTED;
-  PpoArgs a{d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp, advantages,
-            returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, max_grad_norm, exp_avg, exp_avg_sq,
-            (float)beta1, (float)beta2, adam_eps, ws, (hipStream_t)stream};
-  const long long total = (long long)T * n_envs * n_epochs;
-  int64_t step = adam_steps_done;
-  int mb = 0;
-  auto size_at = [&](long long start) { return (int)((total - start) < batch_size ? (total - start) : batch_size); };
-  const Gathered g = gathered_region(d, ws, size_at(0), total);
-  // which epoch kernel (64-wide towers; see below): the word-exchange form has its areas and control words cleared by
-  // the gather launch
-  static int dev_cus = 0;
-  if (dev_cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return IA_ERR_ARG;
-  }
-  constexpr size_t EPOCH_SPLIT_LDS = 160 * 1024 - 1024;   // dynamic LDS the one-tower kernel may ask for (it has static LDS too)
-  constexpr size_t EPOCH_LL_LDS = 160 * 1024 - 2048;
-  const bool one_launch = d->hidden == 64 && !g_epoch_split && g_tstamp == nullptr;
-  const int nrb = cdiv(size_at(0), ROWS);
-  const PolOff po = pol_offsets(d->obs_dim, d->act_dim, d->hidden, d->discrete);
-  const int P = po.total;
-  // one tower per workgroup (two workgroups of four waves per row block, the tower's parameters resident in LDS) when
-  // both fit: 2 nrb workgroups co-resident, chunks of <= 4 x 256 parameters, the larger tower's images beside its tiles
-  const int tlen = 64 * d->obs_dim + 64 + 64 * 64 + 64, lenB = std::max(po.cW - po.aW, P - po.cW) + 3;
-  const size_t sbytes = (size_t)(((GLds<64, 1>::total + 3) & ~3) + 2 * tlen + 4 * d->obs_dim + 128 + lenB + MAXA) * sizeof(float);
-  const bool towers_fit = one_launch && !g_epoch_whole && 2 * nrb <= dev_cus && 2 * nrb <= 64;
-  // the word-exchange form of the one-tower kernel (no grid barriers); its word areas sit behind everything else in ws.
-  // Small minibatches (down to ONE row block: SB3's default batch_size = 64): the launch has as many workgroups as it takes
-  // for chunks of <= 1 024 parameters -- those beyond the row blocks run no gradient phase, they sum, clip and step their
-  // chunk (`epoch_ll_row_blocks`)
-  const int nrb_l = epoch_ll_row_blocks(nrb, P);
-  const bool llx = towers_fit && !g_epoch_barriers && sbytes + 16 <= EPOCH_LL_LDS && nrb_l <= 32 && 2 * nrb_l <= dev_cus;
-  const bool split = towers_fit && sbytes <= EPOCH_SPLIT_LDS && (llx || cdiv(P, 2 * nrb) <= 4 * 256);
-  // round 6: the transposed-chain kernel on 32-ROW blocks (twice the workgroups, half the chain and half the weight-gradient
-  // tiles per compute unit) where its 2 x ceil(b / 32) workgroups and slabs fit the exchange's limits (minibatches <= 1 024 rows)
-  const int nrb32_l = epoch_ll_row_blocks(cdiv(size_at(0), 32), P);
-  const bool rows32 = llx && g_epoch_chain2 && g_epoch_rows32 && d->obs_dim <= 32 && nrb32_l <= 32 && 2 * nrb32_l <= dev_cus &&
-                      2 * nrb32_l <= 64;
-  const int nrb_x = rows32 ? nrb32_l : nrb_l;   // row blocks the word areas are laid out for
-  unsigned long long* ll_base = llx ? reinterpret_cast<unsigned long long*>(ws + ppo_ws_plain_floats(d, size_at(0), total)) : nullptr;
-  int rc = launch_gather(a, perm, total, g, ll_base, llx ? epoch_ll_words(nrb_x, P) : 0,
-                         llx ? reinterpret_cast<unsigned*>(ws) + 4 : nullptr);   // (words 4, 5, 6: counter, error word, ticket)
-  if (rc) return rc;
-  // statistics of every minibatch of the epoch, one launch ahead of the chain (ppo_epoch_stats_kernel)
-  const int aw = d->discrete ? 1 : d->act_dim;
-  const int n_mb = (int)((total + batch_size - 1) / batch_size);
-  float* seq = g.ret + total;                       // [n_mb][EPS_SEQ]
-  float* part = seq + (long long)n_mb * EPS_SEQ;    // [n_mb][EPS_PART]
-  (void)aw;
-  {
-    static bool attr = false;
-    const size_t bytes = PREP_LDS_FLOATS * sizeof(float);
-    if (!attr) { rc = set_lds(ppo_epoch_stats_kernel, bytes); if (rc) return rc; attr = true; }
-    if (!llx && hipMemsetAsync(ws + 6, 0, sizeof(unsigned), a.st) != hipSuccess) return IA_ERR_ARG;   // its ticket (ws is not pre-zeroed)
-    hipLaunchKernelGGL(ppo_epoch_stats_kernel, dim3(n_mb), dim3(PREP_THREADS), bytes, a.st, *d, g.obs, g.adv, total,
-                       batch_size, update_norm, norm_mean, norm_var, norm_count, seq, part,
-                       reinterpret_cast<unsigned*>(ws) + 6);
-    IA_CHECK_LAUNCH();
-  }
-  const bool snap = d->has_norm && update_norm;
-  if (one_launch) {
-    // one launch per (<= 64 minibatches of the) epoch when every gradient workgroup can be resident at once
-    const int nwg = split ? 2 * nrb : nrb;
-    if (llx || (nwg <= dev_cus && nwg <= 64 && cdiv(P, nwg) <= 4 * (split ? 256 : 512))) {
-      static bool attr = false, attr_s = false;
-      const size_t mbytes = split ? sbytes : GLds<64>::total * sizeof(float);
-      const int aw_ = d->discrete ? 1 : d->act_dim;
-      const size_t l2bytes = (size_t)(d->obs_dim <= 16 ? T64Geo<1>(d->obs_dim, aw_).total : T64Geo<2>(d->obs_dim, aw_).total) *
-                                 sizeof(float) + 16;
-      if (llx && g_epoch_chain2 && d->obs_dim <= 32 && l2bytes <= EPOCH_LL_LDS) {
-        // round 5's gradient phase (transposed register-resident chain, images with ds_read_b128 fragments)
-        auto k1h = ppo_epoch_ll2_kernel<1, 8, 64>;   // 64-row blocks: eight waves (feature halves), two per SIMD
-        auto k2h = ppo_epoch_ll2_kernel<2, 8, 64>;
-        auto k1r = ppo_epoch_ll2_kernel<1, 4, 32>;   // round 6: 32-row blocks, feature halves
-        auto k2r = ppo_epoch_ll2_kernel<2, 4, 32>;
-        auto k1q = ppo_epoch_ll2_kernel<1, 8, 32>;   // round 6: 32-row blocks, feature quarters (two waves per SIMD)
-        auto k2q = ppo_epoch_ll2_kernel<2, 8, 32>;
-        const int nw = rows32 ? (g_epoch_quarters ? 8 : 4) : 8;
-        const int ki = (d->obs_dim <= 16 ? 0 : 1) + (rows32 ? (nw == 8 ? 4 : 2) : 0);
-        decltype(k1h) kerns[6] = {k1h, k2h, k1r, k2r, k1q, k2q};
-        auto kern = kerns[ki];
-        static bool attr_2[6] = {false, false, false, false, false, false};
-        if (!attr_2[ki]) { rc = set_lds(kern, EPOCH_LL_LDS); if (rc) return rc; attr_2[ki] = true; }
-        EpochLl el{};
-        el.base = ll_base;   // (cleared, like the error word, by the gather launch above)
-        for (int first = 0; first < n_mb; first += EpochSteps::MAX) {
-          EpochSteps es{};
-          es.first = first;
-          es.n = std::min(EpochSteps::MAX, n_mb - first);
-          el.seq0 = (unsigned)(adam_steps_done + first + 1);
-          for (int k = 0; k < es.n; ++k) {
-            ++step;
-            es.step_size[k] = (float)(lr / (1.0 - pow(beta1, (double)step)));
-            es.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2, (double)step));
-          }
-          hipLaunchKernelGGL(kern, dim3(2 * nrb_x), dim3(64 * nw), l2bytes, a.st, *d, params, params_t, exp_avg, exp_avg_sq, norm_mean,
-                             norm_var, g.obs, g.act, g.logp, g.adv, g.ret, total, batch_size, T, n_envs, normalize_adv,
-                             clip_range, ent_coef, vf_coef, max_grad_norm, (float)beta1, (float)beta2, adam_eps, ws, el, seq,
-                             snap ? 1 : 0, stats, es, g_epoch_dbg);
-          IA_CHECK_LAUNCH();
-        }
-        return IA_OK;
-      }
-      if (llx) {
-        const int nll = tlen <= 20 * 256 ? 20 : (tlen <= 24 * 256 ? 24 : 33);
-        static bool attr_l[3] = {false, false, false};
-        auto k20 = ppo_epoch_ll_kernel<64, 20>;
-        auto k24 = ppo_epoch_ll_kernel<64, 24>;
-        auto k33 = ppo_epoch_ll_kernel<64, 33>;
-        auto kern = nll == 20 ? k20 : (nll == 24 ? k24 : k33);
-        const int ai = nll == 20 ? 0 : (nll == 24 ? 1 : 2);
-        if (!attr_l[ai]) { rc = set_lds(kern, EPOCH_LL_LDS); if (rc) return rc; attr_l[ai] = true; }
-        EpochLl el{};
-        el.base = ll_base;   // (cleared, like the error word, by the gather launch above)
-        for (int first = 0; first < n_mb; first += EpochSteps::MAX) {
-          EpochSteps es{};
-          es.first = first;
-          es.n = std::min(EpochSteps::MAX, n_mb - first);
-          el.seq0 = (unsigned)(adam_steps_done + first + 1);
-          for (int k = 0; k < es.n; ++k) {
-            ++step;
-            es.step_size[k] = (float)(lr / (1.0 - pow(beta1, (double)step)));
-            es.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2, (double)step));
-          }
-          hipLaunchKernelGGL(kern, dim3(2 * nrb_l), dim3(256), sbytes + 16, a.st, *d, params, params_t, exp_avg, exp_avg_sq, norm_mean,
-                             norm_var, g.obs, g.act, g.logp, g.adv, g.ret, total, batch_size, T, n_envs, normalize_adv,
-                             clip_range, ent_coef, vf_coef, max_grad_norm, (float)beta1, (float)beta2, adam_eps, ws, el, seq,
-                             snap ? 1 : 0, stats, es, g_epoch_dbg);
-          IA_CHECK_LAUNCH();
-        }
-        return IA_OK;
-      }
-      if (!split && !attr) { rc = set_lds(ppo_epoch_persistent_kernel<64>, mbytes); if (rc) return rc; attr = true; }
-      if (split && !attr_s) {
-        rc = set_lds(ppo_epoch_persistent_kernel<64, true>, EPOCH_SPLIT_LDS);
-        if (rc) return rc;
-        attr_s = true;
-      }
-      if (hipMemsetAsync(ws + 4, 0, 2 * sizeof(unsigned), a.st) != hipSuccess) return IA_ERR_ARG;   // barrier counter, error word
-      for (int first = 0; first < n_mb; first += EpochSteps::MAX) {
-        EpochSteps es{};
-        es.first = first;
-        es.n = std::min(EpochSteps::MAX, n_mb - first);
-        for (int k = 0; k < es.n; ++k) {
-          ++step;
-          es.step_size[k] = (float)(lr / (1.0 - pow(beta1, (double)step)));
-          es.bc2_sqrt[k] = (float)sqrt(1.0 - pow(beta2, (double)step));
-        }
-        if (first > 0 && hipMemsetAsync(ws + 4, 0, sizeof(unsigned), a.st) != hipSuccess) return IA_ERR_ARG;
-        if (split)
-          hipLaunchKernelGGL((ppo_epoch_persistent_kernel<64, true>), dim3(nwg), dim3(256), mbytes, a.st, *d, params,
-                             params_t, exp_avg, exp_avg_sq, norm_mean, norm_var, g.obs, g.act, g.logp, g.adv, g.ret, total,
-                             batch_size, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, max_grad_norm,
-                             (float)beta1, (float)beta2, adam_eps, ws, seq, snap ? 1 : 0, stats, es, g_epoch_dbg);
-        else
-          hipLaunchKernelGGL(ppo_epoch_persistent_kernel<64>, dim3(nwg), dim3(512), mbytes, a.st, *d, params, params_t,
-                             exp_avg, exp_avg_sq, norm_mean, norm_var, g.obs, g.act, g.logp, g.adv, g.ret, total, batch_size,
-                             T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, max_grad_norm, (float)beta1,
-                             (float)beta2, adam_eps, ws, seq, snap ? 1 : 0, stats, es, g_epoch_dbg);
-        IA_CHECK_LAUNCH();
-      }
-      return IA_OK;
-    }
-  }
-  for (long long start = 0; start < total; start += batch_size, ++mb) {
-    const int b = size_at(start);
-    ++step;
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    PpoArgs v = at_rows(a, g, start);
-    float* sq = seq + (long long)mb * EPS_SEQ;
-    v.advstat = sq;
-    if (snap) { v.norm_mean = sq + 8; v.norm_var = sq + 8 + MAXD; }
-    rc = d->hidden == 32 ? launch_grad<32>(v, nullptr, b) : launch_grad<64>(v, nullptr, b);
-    if (rc) return rc;
-    rc = launch_apply_split(v, b, (float)(lr / bc1), (float)sqrt(bc2), stats ? stats + mb * 8 : nullptr, nullptr, nullptr,
-                            nullptr, 0, 0);
-    if (rc) return rc;
-  }
-  return IA_OK;
-}
-
 
 int ia_ppo_epoch(const ia_policy_desc* d, float* params, float* params_t, float* norm_mean, float* norm_var,
                  int32_t* norm_count, int update_norm, const float* obs, const float* actions, const float* old_logp,
@@ -6486,9 +6662,10 @@ int ia_ppo_epoch(const ia_policy_desc* d, float* params, float* params_t, float*
                  int batch_size, int normalize_adv, float clip_range, float ent_coef, float vf_coef,
                  float max_grad_norm, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2,
                  float adam_eps, int64_t adam_steps_done, float* ws, float* stats, void* stream) {
-  return ppo_epochs_impl(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp,
-                         advantages, returns, perm, 1, T, n_envs, batch_size, normalize_adv, clip_range, ent_coef, vf_coef,
-                         max_grad_norm, exp_avg, exp_avg_sq, lr, beta1, beta2, adam_eps, adam_steps_done, ws, stats, stream);
+  return ppo_epochs_impl(make_args(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp,
+                                   advantages, returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef,
+                                   max_grad_norm, exp_avg, exp_avg_sq, beta1, beta2, adam_eps, ws, stream),
+                         PpoSchedule{perm, 1, batch_size, lr, beta1, beta2, adam_steps_done, stats});
 }
 
 int ia_ppo_epochs(const ia_policy_desc* d, float* params, float* params_t, float* norm_mean, float* norm_var,
@@ -6497,33 +6674,12 @@ int ia_ppo_epochs(const ia_policy_desc* d, float* params, float* params_t, float
                   int batch_size, int normalize_adv, float clip_range, float ent_coef, float vf_coef,
                   float max_grad_norm, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2,
                   float adam_eps, int64_t adam_steps_done, float* ws, float* stats, void* stream) {
-  return ppo_epochs_impl(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp,
-                         advantages, returns, perms, n_epochs, T, n_envs, batch_size, normalize_adv, clip_range, ent_coef,
-                         vf_coef, max_grad_norm, exp_avg, exp_avg_sq, lr, beta1, beta2, adam_eps, adam_steps_done, ws, stats,
-                         stream);
+  return ppo_epochs_impl(make_args(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp,
+                                   advantages, returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef,
+                                   max_grad_norm, exp_avg, exp_avg_sq, beta1, beta2, adam_eps, ws, stream),
+                         PpoSchedule{perms, n_epochs, batch_size, lr, beta1, beta2, adam_steps_done, stats});
 }
 
-// LDS of a gradient block: minibatch tiles, both parameter copies, the staged next minibatch, the transpose map
-inline size_t upd_grad_lds_bytes(int P4, int aw) {
-  return 16 /* base rounded up to 16 bytes */ + (CLds::total + (size_t)P4 + upd_pt4(P4) + UpdStage::total(aw)) * sizeof(float) +
-         P4 * sizeof(unsigned short);
-}
-
-// Workspace of ia_ppo_update in floats; 0 when the persistent kernel does not cover the shape
-// (the caller then runs ia_ppo_epoch per epoch).
-static int64_t upd_ws_floats(const ia_policy_desc* d, int batch_size, int world) {
-  if (!pol_ok(d) || batch_size <= 0 || world < 1 || world > SHARD_WORLD_MAX) return IA_ERR_ARG;
-  const int P = pol_offsets(d->obs_dim, d->act_dim, d->hidden, d->discrete).total;
-  const int nblk = cdiv(batch_size, ROWS);
-  const int P4 = (P + 3) & ~3;
-  if (d->hidden != 32 || P > UPD_NPT_WIDE * 512 || upd_grad_lds_bytes(P4, d->discrete ? 1 : d->act_dim) > 160 * 1024 || nblk > UPD_NBLK_MAX ||
-      cdiv((long long)batch_size * world, UPD_SLICE) > UPD_SLICES_MAX)
-    return 0;
-  // (every gradient workgroup polls nblk x ceil((P4 + 8) / nblk) slab words with its parameters-per-thread x 512 lanes)
-  if (nblk > 1 && P4 + 8 + nblk - 1 > UPD_NPT_WIDE * 512) return 0;
-  return UPD_CTRL + 2 * UPD_MAX_STEPS + UPD_RING * UPD_RS + UPD_SD * 2 + UPD_SD * (int64_t)nblk * 8 +
-         4 * (int64_t)nblk * (P4 + 8) + 4 * (int64_t)(P4 + 8) + (int64_t)UPD_RING * UPD_SLICES_MAX * UPD_PRS;
-}
 int64_t ia_ppo_update_ws_floats(const ia_policy_desc* d, int batch_size) { return upd_ws_floats(d, batch_size, 1); }
 // Row-sharded data-parallel update (ia_ppo_update_sharded): workspace for `rows_per_rank` rows of each global minibatch of
 // world x rows_per_rank rows (0: shape not covered), and the size of a rank's receive area.
@@ -6536,221 +6692,12 @@ int64_t ia_ppo_shard_recv_bytes(const ia_policy_desc* d, int world) {
   return 2 * (int64_t)world * (((P + 3) & ~3) + 8) * (int64_t)sizeof(unsigned long long);
 }
 
-bool g_upd_xcd_pack = false;   // opt-in (ia_ppo_update_xcd_pack): several gradient workgroups that fit one XCD packed there
-constexpr int HOST_TAB_SLOTS = 8;
-struct HostTab { float* buf = nullptr; hipEvent_t done; };
-HostTab g_host_tab[HOST_TAB_SLOTS];
-int g_host_tab_next = 0;
 int ia_ppo_update_xcd_pack(int on) { g_upd_xcd_pack = on != 0; return IA_OK; }
-int g_upd_assume_cus = 0;
 int ia_ppo_update_assume_cus(int n) { g_upd_assume_cus = n; return IA_OK; }
-bool g_upd_tower_split = false;   // (ia_ppo_update_tower_split) two gradient workgroups per row block, one per tower, where they fit
 int ia_ppo_update_tower_split(int on) { g_upd_tower_split = on != 0; return IA_OK; }
-int g_upd_slice_owner = 0;   // (ia_ppo_update_slice_owner) hop 1 of the tower-split form: 0 every gradient workgroup owns a slice,
-                             // 1 the value workgroups own a value and a policy slice each, the policy workgroups none
 int ia_ppo_update_slice_owner(int mode) {
   if (mode != 0 && mode != 1) return IA_ERR_ARG;
   g_upd_slice_owner = mode;
-  return IA_OK;
-}
-
-// A whole PPO.train: n_epochs passes over consecutive minibatches of perm[e][T*n_envs] (SB3
-// RolloutBuffer.get order), in ONE persistent launch per <= UPD_MAX_STEPS optimiser steps.
-// stats: [n_epochs * n_minibatches][8] or NULL. ws must be zero-initialised once by the caller;
-// word 8 of it is a sticky error flag (non-zero: a grid wait timed out, results invalid).
-// `shard` (ia_ppo_update_sharded): `batch_size` is the rank's rows per minibatch, `n_envs` the global tile's width; the
-// schedule (minibatch size world x batch_size, statistics slices) is the global one, the gradient workgroups are the rank's.
-static int ppo_update_launch(const ia_policy_desc* d, float* params, float* params_t, float* norm_mean, float* norm_var,
-                  int32_t* norm_count, int update_norm, const float* obs, const float* actions, const float* old_logp,
-                  const float* advantages, const float* returns, const int64_t* perm, int n_epochs, int T, int n_envs,
-                  int batch_size, int normalize_adv, float clip_range, float ent_coef, float vf_coef,
-                  float max_grad_norm, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2,
-                  float adam_eps, int64_t adam_steps_done, float* ws, float* stats, void* stream, const ShardArgs* shard) {
-  const int world = shard ? shard->world : 1;
-  if (!pol_ok(d) || batch_size <= 0 || n_epochs <= 0 || upd_ws_floats(d, batch_size, world) <= 0) return IA_ERR_ARG;
-  const long long total = (long long)T * n_envs;
-  const int batch_global = batch_size * world;
-  const int n_mb = cdiv(total, batch_global);
-  const int nblk = cdiv(batch_size, ROWS);
-  const int P = pol_offsets(d->obs_dim, d->act_dim, 32, d->discrete).total;
-  const int P4 = (P + 3) & ~3;
-  const size_t grad_bytes = upd_grad_lds_bytes(P4, d->discrete ? 1 : d->act_dim);
-  const size_t prep_bytes = (PREP_LDS_FLOATS + (size_t)cdiv(batch_global, ROWS) * ROWS) * sizeof(float);  // + row offsets
-  const size_t bytes = grad_bytes > prep_bytes ? grad_bytes : prep_bytes;
-  const bool wide = P > UPD_NPT * 512 || (nblk > 1 && P4 + 8 + nblk - 1 > UPD_NPT * 512);
-  const bool timing = g_tstamp != nullptr;
-  // instantiations: {8, 9} parameters per thread x {production, phase clocks} x first-layer fragments for <= 32 / <= 64
-  // observation columns (the narrow form keeps 16 registers less across the chain)
-  const bool ks16 = d->obs_dim > 32;
-  // one gradient workgroup whose parameter vector fits the consumed part of the staging area: the gradient stays in LDS
-  const bool local = nblk == 1 && P4 <= UpdStage::nxt;
-  using KernelT = decltype(&ppo_update_persistent_kernel<UPD_NPT, false, 8, false>);
-  static const KernelT kernels[32] = {
-      ppo_update_persistent_kernel<UPD_NPT, false, 8, false>,      ppo_update_persistent_kernel<UPD_NPT, false, 16, false>,
-      ppo_update_persistent_kernel<UPD_NPT, true, 8, false>,       ppo_update_persistent_kernel<UPD_NPT, true, 16, false>,
-      ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, false>, ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, false>,
-      ppo_update_persistent_kernel<UPD_NPT_WIDE, true, 8, false>,  ppo_update_persistent_kernel<UPD_NPT_WIDE, true, 16, false>,
-      ppo_update_persistent_kernel<UPD_NPT, false, 8, true>,       ppo_update_persistent_kernel<UPD_NPT, false, 16, true>,
-      ppo_update_persistent_kernel<UPD_NPT, true, 8, true>,        ppo_update_persistent_kernel<UPD_NPT, true, 16, true>,
-      ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, true>,  ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, true>,
-      ppo_update_persistent_kernel<UPD_NPT_WIDE, true, 8, true>,   ppo_update_persistent_kernel<UPD_NPT_WIDE, true, 16, true>,
-      // row-sharded data parallelism (no phase-clock build): [16 + local * 4 + wide * 2 + ks16]
-      ppo_update_persistent_kernel<UPD_NPT, false, 8, false, true>,      ppo_update_persistent_kernel<UPD_NPT, false, 16, false, true>,
-      ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, false, true>, ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, false, true>,
-      ppo_update_persistent_kernel<UPD_NPT, false, 8, true, true>,       ppo_update_persistent_kernel<UPD_NPT, false, 16, true, true>,
-      ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, true, true>,  ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, true, true>,
-      // one gradient workgroup, minibatches of <= 16 rows (the tuned AIRL file): six of the eight waves skip the layer chain,
-      // each tower's one wave has a SIMD to itself: [24 + shard * 4 + wide * 2 + ks16]
-      ppo_update_persistent_kernel<UPD_NPT, false, 8, true, false, true>,       ppo_update_persistent_kernel<UPD_NPT, false, 16, true, false, true>,
-      ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, true, false, true>,  ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, true, false, true>,
-      ppo_update_persistent_kernel<UPD_NPT, false, 8, true, true, true>,        ppo_update_persistent_kernel<UPD_NPT, false, 16, true, true, true>,
-      ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 8, true, true, true>,   ppo_update_persistent_kernel<UPD_NPT_WIDE, false, 16, true, true, true>};
-  const bool small = local && batch_size <= 16 && !timing;
-  const int vi_k = small ? 24 + (shard ? 4 : 0) + wide * 2 + ks16
-                         : (shard ? 16 + local * 4 + wide * 2 + ks16 : local * 8 + wide * 4 + timing * 2 + ks16);
-  // One tower per gradient workgroup (`ppo_update_split_kernel`): several gradient workgroups of one process, switch on,
-  // and -- checked per launch below -- 2 nblk + 1 + 2 n_slices workgroups co-resident; otherwise the form above, unchanged.
-  // [owner * 8 + wide * 4 + timing * 2 + ks16]; its own caches of the LDS attribute and the occupancy.
-  // [8 ..]: the same with hop 1's slices by tower on the value workgroups (`ia_ppo_update_slice_owner(1)`)
-  static const KernelT split_kernels[16] = {
-      ppo_update_split_kernel<UPD_NPT, false, 8>,      ppo_update_split_kernel<UPD_NPT, false, 16>,
-      ppo_update_split_kernel<UPD_NPT, true, 8>,       ppo_update_split_kernel<UPD_NPT, true, 16>,
-      ppo_update_split_kernel<UPD_NPT_WIDE, false, 8>, ppo_update_split_kernel<UPD_NPT_WIDE, false, 16>,
-      ppo_update_split_kernel<UPD_NPT_WIDE, true, 8>,  ppo_update_split_kernel<UPD_NPT_WIDE, true, 16>,
-      ppo_update_owner_kernel<UPD_NPT, false, 8>,      ppo_update_owner_kernel<UPD_NPT, false, 16>,
-      ppo_update_owner_kernel<UPD_NPT, true, 8>,       ppo_update_owner_kernel<UPD_NPT, true, 16>,
-      ppo_update_owner_kernel<UPD_NPT_WIDE, false, 8>, ppo_update_owner_kernel<UPD_NPT_WIDE, false, 16>,
-      ppo_update_owner_kernel<UPD_NPT_WIDE, true, 8>,  ppo_update_owner_kernel<UPD_NPT_WIDE, true, 16>};
-  const bool want_split = g_upd_tower_split && shard == nullptr && nblk >= 2;
-  // slices by tower: each of an owner's two passes polls nblk x ceil(set / nblk) words with its parameters-per-thread x 512
-  // lanes (sets: the value elements; the policy elements + 5 loss-statistic words); a pass that does not fit -> ownership 0
-  const PolOff po = pol_offsets(d->obs_dim, d->act_dim, 32, d->discrete);
-  const int n_pol = po.vW1 + (po.cW - po.aW) + 5, n_val = P - (n_pol - 5);
-  const int own_lanes = (wide ? UPD_NPT_WIDE : UPD_NPT) * 512;
-  const bool by_tower = g_upd_slice_owner == 1 && nblk * cdiv(n_pol, nblk) <= own_lanes && nblk * cdiv(n_val, nblk) <= own_lanes;
-  const int vi_s = by_tower * 8 + wide * 4 + timing * 2 + ks16;
-  const KernelT kernel = kernels[vi_k];
-  static size_t attr_bytes[32] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (bytes > attr_bytes[vi_k]) {
-    const int rc = set_lds(kernel, bytes);
-    if (rc) return rc;
-    attr_bytes[vi_k] = bytes;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int steps_total = n_epochs * n_mb;
-  int64_t step = adam_steps_done;
-  for (int first = 0; first < steps_total; first += UPD_MAX_STEPS) {
-    UpdSched sch;
-    sch.n_steps = steps_total - first < UPD_MAX_STEPS ? steps_total - first : UPD_MAX_STEPS;
-    sch.first = first; sch.n_mb = n_mb; sch.batch_size = batch_global; sch.total = total;
-    // Adam's per-step scalars, formed in double on the host exactly as torch.optim.Adam does, staged
-    // through a small ring of pinned buffers (a slot is reused only after its copy has completed).
-    HostTab& ht = g_host_tab[g_host_tab_next];
-    g_host_tab_next = (g_host_tab_next + 1) % HOST_TAB_SLOTS;
-    if (ht.buf == nullptr) {
-      hipError_t e0 = hipHostMalloc(reinterpret_cast<void**>(&ht.buf), 2 * UPD_MAX_STEPS * sizeof(float), 0);
-      if (e0 != hipSuccess) return (int)e0;
-      e0 = hipEventCreateWithFlags(&ht.done, hipEventDisableTiming);
-      if (e0 != hipSuccess) return (int)e0;
-    } else {
-      hipError_t e0 = hipEventSynchronize(ht.done);
-      if (e0 != hipSuccess) return (int)e0;
-    }
-    for (int s = 0; s < sch.n_steps; ++s) {
-      ++step;
-      const double bc1 = 1.0 - pow(beta1, (double)step);
-      const double bc2 = 1.0 - pow(beta2, (double)step);
-      ht.buf[s] = (float)(lr / bc1);
-      ht.buf[UPD_MAX_STEPS + s] = (float)sqrt(bc2);
-    }
-    const UpdWs uw = upd_ws(ws, nblk, P);
-    hipError_t ec = hipMemcpyAsync(uw.tab, ht.buf, 2 * UPD_MAX_STEPS * sizeof(float), hipMemcpyHostToDevice, st);
-    if (ec != hipSuccess) return (int)ec;
-    ec = hipEventRecord(ht.done, st);
-    if (ec != hipSuccess) return (int)ec;
-    hipError_t e = hipMemsetAsync(ws, 0, 8 * sizeof(unsigned), st);  // published / second-level arrivals (error word stays)
-    if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(ws + 16, 0, (UPD_CTRL - 16) * sizeof(unsigned), st);  // per-slicer progress, arrival counters
-    if (e != hipSuccess) return (int)e;
-    // packing onto one XCD only works while all workgroups fit its 32 CUs (each takes a whole CU's LDS)
-    // minibatches beyond UPD_SLICE rows: their statistics are cut into UPD_SLICE-row slices, one extra block
-    // each, merged in order by the statistics block. (One block needs 22 us for the gathered moments of a
-    // 1024-row minibatch -- as long as a whole gradient step, so the chain kept waiting 1-2 us per step for
-    // it; two slices + merge take ~14 us and the ring runs ahead again.)
-    const int n_slices = (batch_global > UPD_SLICE && total < (1ll << 31)) ? cdiv(batch_global, UPD_SLICE) : 0;
-    bool pack = g_upd_xcd_pack && nblk > 1 && nblk + 1 + n_slices <= 32;
-    int grid = (nblk + 1 + n_slices) * (pack ? 8 : 1);
-    KernelT launch_kernel = kernel;
-    if (want_split) {   // the same residency test for the wider grid; no room -> the two-tower form (and ITS test) below
-      static int s_dev_cus = 0, s_per_cu[16] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-      static size_t s_per_cu_bytes[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      static size_t s_attr_bytes[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      if (bytes > s_attr_bytes[vi_s]) {
-        const int rc = set_lds(split_kernels[vi_s], bytes);
-        if (rc) return rc;
-        s_attr_bytes[vi_s] = bytes;
-      }
-      if (s_dev_cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&s_dev_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-          return IA_ERR_ARG;
-      }
-      const int cu_count = g_upd_assume_cus > 0 ? g_upd_assume_cus : s_dev_cus;
-      if (s_per_cu[vi_s] < 0 || s_per_cu_bytes[vi_s] != bytes) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(split_kernels[vi_s]), 512,
-                                                         bytes) != hipSuccess)
-          return IA_ERR_ARG;
-        s_per_cu[vi_s] = nb;
-        s_per_cu_bytes[vi_s] = bytes;
-      }
-      const int split_grid = 2 * nblk + 1 + 2 * n_slices;   // (two workgroups per statistics slice: even / odd steps)
-      if ((long long)s_per_cu[vi_s] * cu_count >= split_grid) {
-        launch_kernel = split_kernels[vi_s];
-        grid = split_grid;
-        pack = false;   // (packing onto one XCD does not apply: twice the workgroups, and they are meant to spread)
-      }
-    }
-    if (launch_kernel == kernel) {
-      // The grid barriers inside need every workgroup resident at once. A plain launch performs no such check
-      // (and a cooperative launch costs +15-19 us per launch, MI355X_MICROARCH.md "coop-launch"), so the same
-      // test is made here: workgroups per CU by the occupancy query (LDS-bound: one) times the CU count.
-      // Not enough room -> IA_ERR_UNSUPPORTED, the caller runs ia_ppo_epoch (two launches per minibatch).
-      static int dev_cus = 0, per_cu[32] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,
-                                            -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-      static size_t per_cu_bytes[32] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      const int vi = vi_k;
-      if (dev_cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-          return IA_ERR_ARG;
-      }
-      const int cu_count = g_upd_assume_cus > 0 ? g_upd_assume_cus : dev_cus;
-      if (per_cu[vi] < 0 || per_cu_bytes[vi] != bytes) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kernel), 512, bytes) !=
-            hipSuccess)
-          return IA_ERR_ARG;
-        per_cu[vi] = nb;
-        per_cu_bytes[vi] = bytes;
-      }
-      if ((long long)per_cu[vi] * cu_count < (pack ? grid / 8 : grid)) return IA_ERR_UNSUPPORTED;
-    }
-    ShardArgs sa;
-    if (shard) {
-      sa = *shard;
-      sa.seq_base = shard->seq_base + (unsigned)first;
-    } else {
-      memset(&sa, 0, sizeof(sa));
-    }
-    hipLaunchKernelGGL(launch_kernel, dim3(grid), dim3(512), bytes, st, *d, params, params_t, exp_avg,
-                       exp_avg_sq, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp, advantages,
-                       returns, perm, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef, max_grad_norm,
-                       (float)beta1, (float)beta2, adam_eps, ws, nblk, n_slices, stats, sch, pack ? 1 : 0, g_tstamp, sa);
-    IA_CHECK_LAUNCH();
-  }
   return IA_OK;
 }
 
@@ -6760,10 +6707,10 @@ int ia_ppo_update(const ia_policy_desc* d, float* params, float* params_t, float
                   int batch_size, int normalize_adv, float clip_range, float ent_coef, float vf_coef,
                   float max_grad_norm, float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2,
                   float adam_eps, int64_t adam_steps_done, float* ws, float* stats, void* stream) {
-  return ppo_update_launch(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp,
-                           advantages, returns, perm, n_epochs, T, n_envs, batch_size, normalize_adv, clip_range, ent_coef,
-                           vf_coef, max_grad_norm, exp_avg, exp_avg_sq, lr, beta1, beta2, adam_eps, adam_steps_done, ws,
-                           stats, stream, nullptr);
+  return ppo_update_launch(make_args(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions,
+                                     old_logp, advantages, returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef,
+                                     max_grad_norm, exp_avg, exp_avg_sq, beta1, beta2, adam_eps, ws, stream),
+                           PpoSchedule{perm, n_epochs, batch_size, lr, beta1, beta2, adam_steps_done, stats}, nullptr);
 }
 
 // The same [SB3 PPO.train] with each GLOBAL minibatch's rows sharded over `world` ranks (one process per GPU): `obs` ...
@@ -6794,10 +6741,11 @@ int ia_ppo_update_sharded(const ia_policy_desc* d, float* params, float* params_
     sa.peer_recv[r] = r < world ? static_cast<unsigned long long*>(peer_recv[r]) : nullptr;
     if (r < world && !sa.peer_recv[r]) return IA_ERR_ARG;
   }
-  return ppo_update_launch(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions, old_logp,
-                           advantages, returns, perm, n_epochs, T, n_envs, rows_per_rank, normalize_adv, clip_range,
-                           ent_coef, vf_coef, max_grad_norm, exp_avg, exp_avg_sq, lr, beta1, beta2, adam_eps,
-                           adam_steps_done, ws, stats, stream, &sa);
+  return ppo_update_launch(make_args(d, params, params_t, norm_mean, norm_var, norm_count, update_norm, obs, actions,
+                                     old_logp, advantages, returns, T, n_envs, normalize_adv, clip_range, ent_coef, vf_coef,
+                                     max_grad_norm, exp_avg, exp_avg_sq, beta1, beta2, adam_eps, ws, stream),
+                           PpoSchedule{perm, n_epochs, rows_per_rank, lr, beta1, beta2, adam_steps_done, stats}, &sa);
 }
 
 }  // extern "C"
+

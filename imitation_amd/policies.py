@@ -247,6 +247,14 @@ class ActorCriticPolicy:
         if self._flat_t is not None:
             L.call("ia_policy_transpose", C.byref(self.desc), L.ptr(self._flat), L.ptr(self._flat_t), L.stream())
 
+    def _ppo_source_args(self, update_norm: int, src, idx) -> tuple:
+        """The 13 leading arguments of every `ia_ppo_minibatch*` / `ia_ppo_epoch*` / `ia_ppo_update*` call: the policy, its
+        feature RunningNorm, the (obs, actions, log-probs, advantages, returns) tensors `src` and the row index tensor."""
+        rn = self.features_extractor.normalize
+        return (C.byref(self.desc), L.ptr(self._flat), L.ptr(self._flat_t),
+                L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
+                L.ptr(rn.count) if rn else None, update_norm, *(L.ptr(t) for t in src), L.ptr(idx))
+
     def set_training_mode(self, mode: bool) -> None:
         self.train(mode)
 

@@ -1149,8 +1149,7 @@ class PPO(OnPolicyAlgorithm):
         g["logp"].copy_(allr[..., D + aw]); g["adv"].copy_(allr[..., D + aw + 1]); g["ret"].copy_(allr[..., D + aw + 2])
         g["perms"].finish()
         g["perm_dev"].copy_(g["perm_host"], non_blocking=True)
-        rn = pol.features_extractor.normalize
-        og = pol.optimizer.param_groups[0]
+        src = (g["obs"], g["acts"], g["logp"], g["adv"], g["ret"])
         if self.update_events is not None:
             self.update_events[0].record()
         form, timed = self._dp_pick_form(g)
@@ -1164,32 +1163,33 @@ class PPO(OnPolicyAlgorithm):
             # rows sharded over the ranks, one record per optimiser step exchanged inside the kernels
             ex = sh["ex"]
             steps = self.n_epochs * (-(-(W * T * n) // g["batch"]))
-            L.call("ia_ppo_update_sharded", C.byref(pol.desc), L.ptr(pol._flat), L.ptr(pol._flat_t),
-                   L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
-                   L.ptr(rn.count) if rn else None, int(rn is not None), L.ptr(g["obs"]), L.ptr(g["acts"]),
-                   L.ptr(g["logp"]), L.ptr(g["adv"]), L.ptr(g["ret"]), L.ptr(g["perm_dev"]), self.n_epochs, T, W * n,
-                   sh["rows"], int(self.normalize_advantage), float(clip_range), float(self.ent_coef),
-                   float(self.vf_coef), float(self.max_grad_norm), L.ptr(pol.optimizer.exp_avg),
-                   L.ptr(pol.optimizer.exp_avg_sq), float(lr), float(og["betas"][0]), float(og["betas"][1]),
-                   float(og["eps"]), pol.optimizer.step_count, L.ptr(sh["ws"]), L.ptr(stats_dev), ex.world, ex.rank,
-                   ex.take_steps(steps), ex.recv, ex.peer_recv, int(ex.loop),
+            L.call("ia_ppo_update_sharded",
+                   *self._ppo_args(src, g["perm_dev"], self.n_epochs, W * n, sh["rows"], sh["ws"], stats_dev, lr, clip_range),
+                   ex.world, ex.rank, ex.take_steps(steps), ex.recv, ex.peer_recv, int(ex.loop),
                    float(self.dp_exchange_timeout_s), L.stream())
             self.dp_sharded_updates = getattr(self, "dp_sharded_updates", 0) + 1
         else:
-            L.call("ia_ppo_update", C.byref(pol.desc), L.ptr(pol._flat), L.ptr(pol._flat_t),
-                   L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
-                   L.ptr(rn.count) if rn else None, int(rn is not None), L.ptr(g["obs"]), L.ptr(g["acts"]), L.ptr(g["logp"]),
-                   L.ptr(g["adv"]), L.ptr(g["ret"]), L.ptr(g["perm_dev"]), self.n_epochs, T, W * n, g["batch"],
-                   int(self.normalize_advantage), float(clip_range), float(self.ent_coef), float(self.vf_coef),
-                   float(self.max_grad_norm), L.ptr(pol.optimizer.exp_avg), L.ptr(pol.optimizer.exp_avg_sq),
-                   float(lr), float(og["betas"][0]), float(og["betas"][1]), float(og["eps"]), pol.optimizer.step_count,
-                   L.ptr(g["ws"]), L.ptr(stats_dev), L.stream())
+            L.call("ia_ppo_update",
+                   *self._ppo_args(src, g["perm_dev"], self.n_epochs, W * n, g["batch"], g["ws"], stats_dev, lr, clip_range),
+                   L.stream())
         if ev is not None:
             ev[1].record()
             g["auto"]["events"].append((form, ev))
         if self.update_events is not None:
             self.update_events[1].record()
         pol.optimizer.step_count += self.n_epochs * self._n_mb
+
+    def _ppo_args(self, src, perm, n_epochs, n_envs, batch, ws, stats, lr, clip_range) -> tuple:
+        """The arguments `ia_ppo_epoch` (`n_epochs` None: it takes none), `ia_ppo_epochs`, `ia_ppo_update` and
+        `ia_ppo_update_sharded` share, in their order up to the stream: `src` = the (obs, actions, log-probs, advantages,
+        returns) tiles of [T, n_envs], `perm` the permutation tensor, `ws` / `stats` the workspace and statistics tensors."""
+        pol = self.policy
+        opt, og = pol.optimizer, pol.optimizer.param_groups[0]
+        return (*pol._ppo_source_args(int(pol.features_extractor.normalize is not None), src, perm),
+                *(() if n_epochs is None else (n_epochs,)), self.rollout_buffer.buffer_size, n_envs, batch,
+                int(self.normalize_advantage), float(clip_range), float(self.ent_coef), float(self.vf_coef),
+                float(self.max_grad_norm), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), float(lr), float(og["betas"][0]),
+                float(og["betas"][1]), float(og["eps"]), opt.step_count, L.ptr(ws), L.ptr(stats))
 
     _DP_AUTO_TRIALS = 4   # timed updates of the "auto" choice: sharded / replicated alternating, the first of each discarded
                           # (the driver's five warm-up rounds hold the trials and the verdict)
@@ -1273,10 +1273,9 @@ class PPO(OnPolicyAlgorithm):
                     L.call("ia_gather_rows", L.ptr(obs_rows), L.ptr(offs[e, start:start + b]), b, pol.obs_dim,
                            L.ptr(self._dp_obs), L.stream())
                     rn.update_stats(self._dp_obs, ldx=pol.obs_dim, rows=b)
-                L.call("ia_ppo_minibatch_grad", C.byref(pol.desc), L.ptr(pol._flat), L.ptr(pol._flat_t),
-                       L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
-                       L.ptr(rn.count) if rn else None, 0, L.ptr(rb.obs), L.ptr(rb.acts), L.ptr(rb.logp),
-                       L.ptr(rb.adv), L.ptr(rb.ret), L.ptr(idx), b, T, n, int(self.normalize_advantage),
+                L.call("ia_ppo_minibatch_grad",
+                       *pol._ppo_source_args(0, (rb.obs, rb.acts, rb.logp, rb.adv, rb.ret), idx), b, T, n,
+                       int(self.normalize_advantage),
                        float(clip_range), float(self.ent_coef), float(self.vf_coef), L.ptr(self._ppo_ws), L.stream())
                 off = int(L.load().ia_ppo_grad_offset(C.byref(pol.desc), b))
                 dp.allreduce_mean_(self._ppo_ws[off:off + P])
@@ -1319,8 +1318,7 @@ class PPO(OnPolicyAlgorithm):
                 th.cuda.current_stream().wait_event(early)   # would sit between the last env step and the update
             else:
                 self._perm_dev.copy_(self._perm_host, non_blocking=True)
-        rn = pol.features_extractor.normalize
-        g = pol.optimizer.param_groups[0]
+        src = (rb.obs, rb.acts, rb.logp, rb.adv, rb.ret)
         rec = None
         if self.defer_train_stats:
             if self._records is None:
@@ -1344,14 +1342,8 @@ class PPO(OnPolicyAlgorithm):
             if self.update_events is not None:  # measurement hook (bench.py): events on the launch stream
                 self.update_events[0].record()
             rc = L.load().ia_ppo_update(
-                C.byref(pol.desc), L.ptr(pol._flat), L.ptr(pol._flat_t),
-                L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
-                L.ptr(rn.count) if rn else None, int(rn is not None), L.ptr(rb.obs), L.ptr(rb.acts), L.ptr(rb.logp),
-                L.ptr(rb.adv), L.ptr(rb.ret), L.ptr(self._perm_dev), self.n_epochs, T, n, min(self.batch_size, T * n),
-                int(self.normalize_advantage), float(clip_range), float(self.ent_coef), float(self.vf_coef),
-                float(self.max_grad_norm), L.ptr(pol.optimizer.exp_avg), L.ptr(pol.optimizer.exp_avg_sq),
-                float(lr), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), pol.optimizer.step_count,
-                L.ptr(self._upd_ws), L.ptr(stats_dev), L.stream())
+                *self._ppo_args(src, self._perm_dev, self.n_epochs, n, min(self.batch_size, T * n), self._upd_ws, stats_dev,
+                                lr, clip_range), L.stream())
             if rc == L.ERR_UNSUPPORTED:
                 # not every workgroup of the persistent kernel would be resident at once on this device (its grid
                 # barriers need that): nothing was launched; this and all later updates take the per-epoch kernels
@@ -1372,27 +1364,16 @@ class PPO(OnPolicyAlgorithm):
             # every epoch of the update as one sequence of minibatches (the rollout divides into whole minibatches): gather
             # and statistics of all epochs in one launch each, the epoch kernels back to back
             rc = L.load().ia_ppo_epochs(
-                C.byref(pol.desc), L.ptr(pol._flat), L.ptr(pol._flat_t),
-                L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
-                L.ptr(rn.count) if rn else None, int(rn is not None), L.ptr(rb.obs), L.ptr(rb.acts), L.ptr(rb.logp),
-                L.ptr(rb.adv), L.ptr(rb.ret), L.ptr(self._perm_dev), self.n_epochs, T, n, self.batch_size,
-                int(self.normalize_advantage), float(clip_range), float(self.ent_coef), float(self.vf_coef),
-                float(self.max_grad_norm), L.ptr(pol.optimizer.exp_avg), L.ptr(pol.optimizer.exp_avg_sq),
-                float(lr), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), pol.optimizer.step_count,
-                L.ptr(self._ppo_ws), L.ptr(stats_dev), L.stream())
+                *self._ppo_args(src, self._perm_dev, self.n_epochs, n, self.batch_size, self._ppo_ws, stats_dev, lr,
+                                clip_range), L.stream())
             if rc != L.ERR_UNSUPPORTED:
                 L.check(rc, "ia_ppo_epochs")
                 pol.optimizer.step_count += self.n_epochs * self._n_mb
                 per_epoch = False
         for e in range(self.n_epochs if per_epoch else 0):
-            L.call("ia_ppo_epoch", C.byref(pol.desc), L.ptr(pol._flat), L.ptr(pol._flat_t),
-                   L.ptr(rn.running_mean) if rn else None, L.ptr(rn.running_var) if rn else None,
-                   L.ptr(rn.count) if rn else None, int(rn is not None), L.ptr(rb.obs), L.ptr(rb.acts), L.ptr(rb.logp),
-                   L.ptr(rb.adv), L.ptr(rb.ret), L.ptr(self._perm_dev[e]), T, n, self.batch_size,
-                   int(self.normalize_advantage), float(clip_range), float(self.ent_coef), float(self.vf_coef),
-                   float(self.max_grad_norm), L.ptr(pol.optimizer.exp_avg), L.ptr(pol.optimizer.exp_avg_sq),
-                   float(lr), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), pol.optimizer.step_count,
-                   L.ptr(self._ppo_ws), L.ptr(stats_dev[e]), L.stream())
+            L.call("ia_ppo_epoch",
+                   *self._ppo_args(src, self._perm_dev[e], None, n, self.batch_size, self._ppo_ws, stats_dev[e], lr, clip_range),
+                   L.stream())
             pol.optimizer.step_count += self._n_mb
         self._n_updates += self.n_epochs
         if rec is not None:
