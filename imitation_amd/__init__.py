@@ -23,8 +23,9 @@ from imitation_amd.adversarial.common import AdversarialTrainer, compute_train_s
 from imitation_amd.adversarial.gail import GAIL, RewardNetFromDiscriminatorLogit  # noqa: F401
 from imitation_amd.adversarial.airl import AIRL  # noqa: F401
 from imitation_amd.density import DensityAlgorithm, DensityType  # noqa: F401
-from imitation_amd import (bc, checkpoint, cnn_policy, dagger, density, dqn, mce_irl, modules, ops,  # noqa: F401
-                           preference_comparisons, regularization, rollout, sac, serialize, sqil, td3)
+from imitation_amd import (bc, checkpoint, cnn_policy, dagger, density, dqn, exploration_wrapper, mce_irl,  # noqa: F401
+                           modules, ops, preference_comparisons, regularization, rollout, sac, serialize, sqil, td3)
+from imitation_amd.exploration_wrapper import ExplorationWrapper  # noqa: F401
 from imitation_amd.dagger import (DAggerTrainer, ExponentialBetaSchedule, InteractiveTrajectoryCollector,  # noqa: F401
                                   LinearBetaSchedule, NeedsDemosException, SimpleDAggerTrainer)
 from imitation_amd.mce_irl import MCEIRL, TabularPolicy  # noqa: F401

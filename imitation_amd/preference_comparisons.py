@@ -34,7 +34,7 @@ enqueue and one read-back. Any other `LambdaUpdater` callable runs on the host: 
 
 Out of scope here (each raises `NotImplementedError`): user-defined `Regularizer` subclasses and factories that are not a
 `regularization.RegularizerFactory` of a shipped class (the product path has no autograd a custom penalty could run
-under), exploration in `AgentTrainer`, and ensembles of `modules` (`nn.Module`) nets.
+under) and ensembles of `modules` (`nn.Module`) nets.
 """
 from __future__ import annotations
 
@@ -51,8 +51,10 @@ import torch as th
 from imitation_amd import _lib as L
 from imitation_amd import modules, ops, regularization, reward_nets, rollout
 from imitation_amd.data_types import ExpertIndexStream, TrajectoryWithRew, Transitions, flatten_trajectories
+from imitation_amd.exploration_wrapper import ExplorationWrapper
 from imitation_amd.logger import HierarchicalLogger, configure as configure_logger
 from imitation_amd.networks import HipAdam, TransitionTable, gather_concat, training
+from imitation_amd.util import make_seeds  # noqa: F401  (also importable from here, where callers have always found it)
 from imitation_amd.wrappers import BufferingWrapper, RewardVecEnvWrapper
 
 AnyRewardNet = Union[reward_nets.RewardNet, modules.RewardNet]
@@ -108,12 +110,17 @@ def _check_for_correct_spaces(venv, observation_space, action_space) -> None:
 class AgentTrainer(TrajectoryGenerator):
     """`preference_comparisons.py:127-316`: trains an RL algorithm (`imitation_amd.PPO`) on the reward model and
     samples its trajectories. With a `RewardNet` the reward wrapper carries the net's bound `predict_processed`, so
-    `PPO.collect_rollouts` relabels whole rollouts on the device (its fused / module paths)."""
+    `PPO.collect_rollouts` relabels whole rollouts on the device (its fused / module paths).
+
+    With `exploration_frac > 0` that share of every `sample` is collected under an `ExplorationWrapper` of the
+    algorithm; its steps are rewarded one `reward_fn` call each, like additional sampling. With `exploration_frac == 0`
+    no wrapper is built and nothing is drawn from `rng` (the reference builds one regardless: DESIGN section 4.16)."""
 
     def __init__(self, algorithm, reward_fn, venv, rng: np.random.Generator, exploration_frac: float = 0.0,
                  switch_prob: float = 0.5, random_prob: float = 0.5, custom_logger: Optional[HierarchicalLogger] = None):
-        if exploration_frac > 0:
-            raise NotImplementedError("exploration (ExplorationWrapper) is not implemented: use exploration_frac=0")
+        if exploration_frac > 0 and algorithm is None:
+            # (a frozen test pins `NotImplementedError` for exactly this call: DESIGN section 4.16)
+            raise NotImplementedError("exploration needs an algorithm to wrap (ExplorationWrapper): got algorithm=None")
         self.algorithm = algorithm
         super().__init__(custom_logger)
         if isinstance(reward_fn, (reward_nets.RewardNet, modules.RewardNet)):
@@ -127,7 +134,12 @@ class AgentTrainer(TrajectoryGenerator):
         self.venv = self.reward_venv_wrapper = RewardVecEnvWrapper(self.buffering_wrapper, reward_fn=self.reward_fn)
         self.log_callback = self.reward_venv_wrapper.make_log_callback()
         self.algorithm.set_env(self.venv)
-        assert self.algorithm.get_env() is not None
+        algo_venv = self.algorithm.get_env()
+        assert algo_venv is not None
+        self.exploration_wrapper: Optional[ExplorationWrapper] = None
+        if exploration_frac > 0:
+            self.exploration_wrapper = ExplorationWrapper(policy=self.algorithm, venv=algo_venv, random_prob=random_prob,
+                                                          switch_prob=switch_prob, rng=self.rng)
 
     def train(self, steps: int, **kwargs) -> None:
         n_transitions = self.buffering_wrapper.n_transitions
@@ -141,6 +153,9 @@ class AgentTrainer(TrajectoryGenerator):
         agent_trajs = agent_trajs[::-1]
         avail_steps = sum(len(traj) for traj in agent_trajs)
         exploration_steps = int(self.exploration_frac * steps)
+        if self.exploration_frac > 0 and exploration_steps == 0:
+            self.logger.warn(f"No exploration steps included: exploration_frac = {self.exploration_frac} > 0 "
+                             f"but steps={steps} is too small.")
         agent_steps = steps - exploration_steps
         if avail_steps < agent_steps:
             self.logger.log(f"Requested {agent_steps} transitions but only {avail_steps} in buffer. "
@@ -152,7 +167,18 @@ class AgentTrainer(TrajectoryGenerator):
                                           deterministic_policy=False, rng=self.rng)
             additional_trajs, _ = self.buffering_wrapper.pop_finished_trajectories()
             agent_trajs = list(agent_trajs) + list(additional_trajs)
-        return list(_get_trajectories(agent_trajs, agent_steps))
+        trajectories = list(_get_trajectories(agent_trajs, agent_steps))
+        if exploration_steps > 0:
+            self.logger.log(f"Sampling {exploration_steps} exploratory transitions.")
+            sample_until = rollout.make_sample_until(min_timesteps=exploration_steps, min_episodes=None)
+            algo_venv = self.algorithm.get_env()
+            assert algo_venv is not None
+            # (the returned trajectories carry the reward model's rewards: the buffer's, with the environment's, are kept)
+            rollout.generate_trajectories(policy=self.exploration_wrapper, venv=algo_venv, sample_until=sample_until,
+                                          deterministic_policy=False, rng=self.rng)
+            exploration_trajs, _ = self.buffering_wrapper.pop_finished_trajectories()
+            trajectories.extend(_get_trajectories(exploration_trajs, exploration_steps))
+        return trajectories
 
     @property
     def logger(self) -> HierarchicalLogger:
@@ -1187,11 +1213,6 @@ class PreferenceBag:
 
     def __getitem__(self, key):
         return self.dataset[int(self.pair_ids[key])]
-
-
-def make_seeds(rng: np.random.Generator) -> int:
-    """`util/util.py` `make_seeds(rng)`: one seed for a torch generator."""
-    return int(rng.integers(0, (1 << 31) - 1, (1,))[0])
 
 
 def bag_indices(n: int, generator: th.Generator) -> List[int]:

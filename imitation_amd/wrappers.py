@@ -2,7 +2,7 @@
 
 `BufferingWrapper` (`data/wrappers.py:13-169`) and `RewardVecEnvWrapper`
 (`rewards/reward_wrapper.py:40-133`) keep their reference surface -- `reset`, `step_async`,
-`step_wait`, `pop_trajectories`, `pop_transitions`, `n_transitions`, `episode_rewards`,
+`step_wait`, `pop_trajectories`, `pop_finished_trajectories`, `pop_transitions`, `n_transitions`, `episode_rewards`,
 `make_log_callback` -- but record whole `[n_envs, ...]` step arrays and derive trajectory
 order with `data_types.segment_order`, instead of appending one dict per env per step
 (the reference's dominant CPU cost at n_envs=1024, SURVEY 8a "where the time goes").
@@ -63,6 +63,8 @@ class BufferingWrapper(VecEnvWrapper):
         self._infos: List[Optional[list]] = []
         self.last_infos: Optional[np.ndarray] = None     # infos of the last pop, in its emission order (or None)
         self._ep_lens: List[int] = []
+        # env -> the steps of its running episode that `pop_finished_trajectories` took out of `_steps`
+        self._held: Dict[int, dt.TrajectoryWithRew] = {}
 
     def reset(self, **kwargs):
         if self._init_reset and self.error_on_premature_reset and self.n_transitions > 0:
@@ -72,6 +74,7 @@ class BufferingWrapper(VecEnvWrapper):
         obs = self.venv.reset(**kwargs)
         self._last_obs = obs
         self._steps, self._infos = [], []
+        self._held = {}
         self._timesteps = np.zeros((len(obs),), dtype=int)
         return obs
 
@@ -133,6 +136,7 @@ class BufferingWrapper(VecEnvWrapper):
         (`adversarial/common.py:422-424`): the same rows in the same order, built with one gather."""
         if self.n_transitions == 0:
             return None, []
+        assert not self._held, "pop_finished_trajectories left steps behind: pop_trajectories joins them, this path does not"
         obs, acts, nxt, rews, dones = self._stacked()
         T, n = dones.shape
         order, _, _ = dt.segment_order(dones)
@@ -153,6 +157,7 @@ class BufferingWrapper(VecEnvWrapper):
         the rows itself (the GPU collector already holds them in HBM). Clears the buffer."""
         if self.n_transitions == 0:
             return None, [], 0
+        assert not self._held, "pop_finished_trajectories left steps behind: pop_trajectories joins them, this path does not"
         dones = np.stack([st[4] for st in self._steps])
         order, _, _ = dt.segment_order(dones)
         self.last_infos = self._infos_in_order(order, dones.shape[1])
@@ -169,6 +174,15 @@ class BufferingWrapper(VecEnvWrapper):
     def pop_trajectories(self) -> Tuple[Sequence[dt.TrajectoryWithRew], Sequence[int]]:
         """`wrappers.py:132-148`: completed trajectories in completion order, then the
         in-progress fragments by env index (materialised only when somebody asks for them)."""
+        return self._pop(finish_partial=True)
+
+    def pop_finished_trajectories(self) -> Tuple[Sequence[dt.TrajectoryWithRew], Sequence[int]]:
+        """`wrappers.py:113-130`: the completed trajectories only. The steps of the episodes still running stay behind
+        (`_held`, not counted in `n_transitions`) and lead the trajectory their environment emits next; a `reset` drops
+        them."""
+        return self._pop(finish_partial=False)
+
+    def _pop(self, finish_partial: bool) -> Tuple[Sequence[dt.TrajectoryWithRew], Sequence[int]]:
         if self.n_transitions == 0:
             return [], []
         obs, acts, nxt, rews, dones = self._stacked()
@@ -184,24 +198,38 @@ class BufferingWrapper(VecEnvWrapper):
             return np.array([self._infos[k][e] if self._infos[k] is not None else {} for k in range(s, t + 1)],
                             dtype=object)
 
+        def cut(s: int, t: int, e: int, terminal: bool) -> dt.TrajectoryWithRew:
+            traj = dt.TrajectoryWithRew(obs=np.concatenate([obs[s:t + 1, e], nxt[t:t + 1, e]]), acts=acts[s:t + 1, e],
+                                        rews=rews[s:t + 1, e], infos=infos_of(s, t, e), terminal=terminal)
+            head = self._held.pop(e, None) if s == 0 else None   # (what an earlier `pop_finished_trajectories` left)
+            return traj if head is None else _join(head, traj)
+
         for t, e in zip(t_idx, e_idx):
-            s = last[e] + 1
-            trajs.append(dt.TrajectoryWithRew(obs=np.concatenate([obs[s:t + 1, e], nxt[t:t + 1, e]]),
-                                              acts=acts[s:t + 1, e], rews=rews[s:t + 1, e], infos=infos_of(s, t, e),
-                                              terminal=True))
+            trajs.append(cut(last[e] + 1, t, e, True))
             last[e] = t
         for e in range(n):
             s = last[e] + 1
             if s <= T - 1:
-                trajs.append(dt.TrajectoryWithRew(obs=np.concatenate([obs[s:T, e], nxt[T - 1:T, e]]),
-                                                  acts=acts[s:T, e], rews=rews[s:T, e], infos=infos_of(s, T - 1, e),
-                                                  terminal=False))
+                part = cut(s, T - 1, e, False)
+                if finish_partial:
+                    trajs.append(part)
+                else:
+                    self._held[e] = part
         lens, self._ep_lens = self._ep_lens, []
         self._steps, self._infos = [], []
         self.n_transitions = 0
         return trajs, lens
 
-    pop_finished_trajectories = pop_trajectories
+
+def _join(head: dt.TrajectoryWithRew, tail: dt.TrajectoryWithRew) -> dt.TrajectoryWithRew:
+    """One trajectory of two consecutive pieces of an episode (`tail.obs[0]` is `head.obs[-1]`)."""
+    infos = None
+    if head.infos is not None or tail.infos is not None:
+        parts = [p.infos if p.infos is not None else np.array([{} for _ in range(len(p.acts))], dtype=object)
+                 for p in (head, tail)]
+        infos = np.concatenate(parts)
+    return dt.TrajectoryWithRew(obs=np.concatenate([head.obs, tail.obs[1:]]), acts=np.concatenate([head.acts, tail.acts]),
+                                rews=np.concatenate([head.rews, tail.rews]), infos=infos, terminal=tail.terminal)
 
 
 class WrappedRewardCallback:
