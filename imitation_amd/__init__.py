@@ -29,7 +29,7 @@ from imitation_amd.exploration_wrapper import ExplorationWrapper  # noqa: F401
 from imitation_amd.dagger import (DAggerTrainer, ExponentialBetaSchedule, InteractiveTrajectoryCollector,  # noqa: F401
                                   LinearBetaSchedule, NeedsDemosException, SimpleDAggerTrainer)
 from imitation_amd.mce_irl import MCEIRL, TabularPolicy  # noqa: F401
-from imitation_amd.dqn import DQN, DQNPolicy, QNetwork  # noqa: F401
+from imitation_amd.dqn import DQN, CnnPolicy, CnnQNetwork, DQNPolicy, QNetwork  # noqa: F401
 from imitation_amd.sqil import SQIL, SQILReplayBuffer  # noqa: F401
 from imitation_amd.td3 import DDPG, TD3, Actor, ContinuousCritic, NormalActionNoise, TD3Policy  # noqa: F401
 from imitation_amd.sac import SAC, SACPolicy  # noqa: F401

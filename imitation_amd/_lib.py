@@ -317,6 +317,7 @@ _SIGS = {
     "ia_dqn_q_values": ([_I, _I, _I, _P, _P, _I, _P, _P, _P], C.c_int),
     "ia_dqn_td_loss": ([_P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P], C.c_int),
     "ia_polyak_update": ([_P, _P, _L, _F, _P], C.c_int),
+    "ia_dqn_assemble_u8": ([_P] * 5 + [_L] + [_P] * 5 + [_L, _P, _I, _I, _L] + [_P] * 6, C.c_int),
     "ia_td3_assemble": ([_P] * 5 + [_L] + [_P] * 5 + [_L, _P] + [_I] * 5 + [_P] * 6, C.c_int),
     "ia_td3_target_input": ([_P, _P, _P, _I, _I, _I, _I, _F, _P, _P], C.c_int),
     "ia_td3_critic_loss": ([_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P], C.c_int),

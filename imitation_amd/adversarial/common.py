@@ -102,6 +102,10 @@ class AdversarialTrainer(abc.ABC):
         self.allow_variable_horizon = allow_variable_horizon
         self._horizon = None
         self.venv = venv
+        if isinstance(gen_algo, dqn.DQN) and getattr(gen_algo.policy, "frames", False):
+            raise NotImplementedError("adversarial training over a DQN generator with a CnnPolicy is not implemented: the "
+                                      "relabel-and-store step (ia_offpolicy_step) reads float32 rows, the learner's ring "
+                                      "holds uint8 frames")
         self.gen_algo = gen_algo
         # the replay ring's index rows of a round's discriminator updates are drawn by the PPO permutation helper's C call,
         # behind the epoch permutations, on a copy of NumPy's global generator (`_replay_rows_spec`, `_disc_round`)

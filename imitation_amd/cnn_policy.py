@@ -16,6 +16,9 @@ observations -- the same rollout / update protocol as `general_policy.GeneralTow
 `make_multinomial_step`, `values_rows`, `log_prob_rows`, `ppo_update`): rollout tiles hold the frames as fp32 rows
 (0..255, exact), the policy turns them back into uint8 images on the device. Categorical (Discrete) and DiagGaussian
 (Box) heads. Column buffers are explicit (sized for 288 GB of HBM).
+
+`NatureCnnTrunk` holds what is the extractor's alone -- geometry, layouts, batch buffers, the launches up to `feat` and back
+from `dfeat` -- and is shared with DQN's Q-network (`dqn.CnnQNetwork`); `ActorCriticCnnPolicy` adds the two heads.
 """
 from __future__ import annotations
 
@@ -48,35 +51,16 @@ class NatureCNN:
         self.normalize = None
 
 
-class ActorCriticCnnPolicy:
-    def __init__(self, observation_space, action_space, lr_schedule, net_arch=None, activation_fn=nn.Tanh,
-                 ortho_init: bool = True, use_sde: bool = False, log_std_init: float = 0.0,
-                 features_extractor_class=NatureCNN, features_extractor_kwargs=None, share_features_extractor: bool = True,
-                 normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs=None):
-        if not _is_image_space(observation_space):
-            raise ValueError("ActorCriticCnnPolicy is for uint8 image spaces [C, H, W] with bounds 0 / 255")
-        self.discrete = isinstance(action_space, spaces.Discrete)
-        if not self.discrete and not (isinstance(action_space, spaces.Box) and len(action_space.shape) == 1):
-            raise NotImplementedError("image policies implement Discrete (Categorical) and 1-D Box (DiagGaussian) heads")
-        if net_arch not in (None, [], {}):
-            raise NotImplementedError("hidden layers behind NatureCNN are not implemented (SB3's default is none)")
-        if features_extractor_class is not NatureCNN or not normalize_images:
-            raise NotImplementedError("only NatureCNN on [0, 255] frames is implemented")
-        self.observation_space, self.action_space = observation_space, action_space
-        self.features_dim = int((features_extractor_kwargs or {}).get("features_dim", 512))
-        self.features_extractor = NatureCNN(observation_space, self.features_dim)
-        self.act_dim = int(action_space.n) if self.discrete else int(action_space.shape[0])
-        self.n_actions = self.act_dim               # width of the action head (logits or Gaussian means)
+class NatureCnnTrunk:
+    """The NatureCNN feature extractor on the device, shared by `ActorCriticCnnPolicy` and `dqn.CnnQNetwork`: geometry,
+    the flat parameter buffer with its layouts, the batch buffers, the forward up to `feat` and the backward from `dfeat`.
+    A subclass builds its heads' host modules, hands all of them to `_set_flat` and runs its heads around
+    `_forward_trunk` / `_backward_trunk`."""
+
+    def _init_trunk(self, observation_space, features_dim: int) -> None:
+        self.observation_space = observation_space
+        self.features_dim = int(features_dim)
         self.obs_dim = int(np.prod(observation_space.shape))
-        self.fused = False                          # PPO runs this policy's own minibatch loop (`ppo_update`)
-        self.discrete_sampling = "multinomial"
-        self.training = True
-        self.optimizer_kwargs = dict(optimizer_kwargs or {})
-        self.optimizer_kwargs.setdefault("eps", 1e-5)   # SB3 ActorCriticPolicy default for Adam
-        self.optimizer = None
-        self._low = self._high = None
-        if optimizer_class is not th.optim.Adam:
-            raise NotImplementedError("the PPO step implements Adam (SB3 default)")
         Cin, H, W = observation_space.shape
         self.geom: List[Tuple[int, int, int, int, int, int, int, int]] = []   # (Cin, H, W, Cout, K, S, OH, OW)
         for cout, k, s in _CONVS:
@@ -100,43 +84,41 @@ class ActorCriticCnnPolicy:
         # False: the explicit pair (tests compare the two).
         self.implicit_dgrad = True
         self._dgrad_idx: Dict[int, th.Tensor] = {}
-        # Host construction in SB3's order so that torch's global generator is consumed identically:
-        # the three convolutions, the linear layer, action_net, value_net; then orthogonal re-initialisation
-        # (features extractor sqrt(2), action_net 0.01, value_net 1).
-        C0 = observation_space.shape[0]
+        self.device = th.device("cpu")
+        self._bufs: Dict[int, Dict[str, th.Tensor]] = {}
+        self._pending_reduce: list = []   # (slabs, splits, n, destination piece of the flat gradient) queued by `_wgrad`
+
+    def _host_trunk(self) -> Tuple[nn.Sequential, nn.Sequential]:
+        """The extractor's host modules in SB3's order (torch's default initialisation, its draws from the global
+        generator): the three convolutions, then the linear layer."""
+        C0 = self.observation_space.shape[0]
         cnn = nn.Sequential(nn.Conv2d(C0, 32, 8, 4), nn.ReLU(), nn.Conv2d(32, 64, 4, 2), nn.ReLU(),
                             nn.Conv2d(64, 64, 3, 1), nn.ReLU(), nn.Flatten())
         linear = nn.Sequential(nn.Linear(self.n_flatten, self.features_dim), nn.ReLU())
-        action_net = nn.Linear(self.features_dim, self.n_actions)
-        log_std = None if self.discrete else th.ones(self.act_dim) * log_std_init
-        value_net = nn.Linear(self.features_dim, 1)
-        if ortho_init:
-            def init(m, gain):
-                if isinstance(m, (nn.Linear, nn.Conv2d)):
-                    nn.init.orthogonal_(m.weight, gain=gain)
-                    m.bias.data.fill_(0.0)
-            for mod, gain in ((cnn, np.sqrt(2)), (linear, np.sqrt(2)), (action_net, 0.01), (value_net, 1)):
-                mod.apply(functools.partial(init, gain=gain))
-        mods = [cnn[0], cnn[2], cnn[4], linear[0], action_net, value_net]
-        self._names = ["features_extractor.cnn.0", "features_extractor.cnn.2", "features_extractor.cnn.4",
-                       "features_extractor.linear.0", "action_net", "value_net"]
+        return cnn, linear
+
+    def _set_flat(self, names: List[str], mods: List[nn.Module], first: List[th.Tensor]) -> None:
+        """The flat parameter buffer in torch `parameters()` order: `first` (a policy's own parameters), then the weight (in
+        device layout) and the bias of every module of `mods` -- conv 0 / 2 / 4, linear.0, then the heads."""
+        self._names = list(names)
         self._shapes = [tuple(m.weight.shape) for m in mods]
-        # torch `parameters()` order: the policy's own parameter (log_std, Box heads) first, then the child modules
-        parts: List[th.Tensor] = [] if self.discrete else [log_std]
+        parts: List[th.Tensor] = list(first)
         for i, m in enumerate(mods):
             w = m.weight.detach()
             parts += [self._to_device_layout(i, w).reshape(-1), m.bias.detach().reshape(-1)]
         self._flat = th.cat(parts).contiguous()
         self._offsets: List[Tuple[int, int, int, int]] = []   # (w offset, w numel, b offset, b numel)
-        o = 0 if self.discrete else self.act_dim
+        o = sum(int(t.numel()) for t in first)
         for shp in self._shapes:
             nw, nb = int(np.prod(shp)), int(shp[0])
             self._offsets.append((o, nw, o + nw, nb))
             o += nw + nb
-        self.device = th.device("cpu")
-        self._lr0 = float(lr_schedule(1))
-        self._bufs: Dict[int, Dict[str, th.Tensor]] = {}
-        self._pending_reduce: list = []   # (slabs, splits, n, destination piece of the flat gradient) queued by `_wgrad`
+
+    def _resolve_conv1(self) -> None:
+        """On the device: whether the implicit first layer covers the frame shape (unless a caller forced a choice)."""
+        if self.implicit_conv1 is None:
+            c0, h0, w0 = self.observation_space.shape
+            self.implicit_conv1 = bool(L.load().ia_conv1_u8_implicit_ok(c0, h0, w0, 8, 8, 4, 32))
 
     # ---- layouts ---------------------------------------------------------------------------------------
     def _to_device_layout(self, i: int, w: th.Tensor) -> th.Tensor:
@@ -165,82 +147,10 @@ class ActorCriticCnnPolicy:
         _, _, o, n = self._offsets[i]
         return self._flat[o:o + n]
 
-    def to(self, device):
-        from imitation_amd.networks import HipAdam
-        self.device = th.device(device)
-        self._flat = self._flat.to(self.device).contiguous()
-        if self.device.type == "cuda":
-            if self.implicit_conv1 is None:
-                c0, h0, w0 = self.observation_space.shape
-                self.implicit_conv1 = bool(L.load().ia_conv1_u8_implicit_ok(c0, h0, w0, 8, 8, 4, 32))
-            self.optimizer = HipAdam(self._flat, th.zeros_like(self._flat), lr=self._lr0, **self.optimizer_kwargs)
-            if self.discrete:
-                self._low = self._high = th.zeros(self.act_dim, device=self.device)
-            else:
-                self._low = th.as_tensor(self.action_space.low.reshape(-1), dtype=th.float32, device=self.device)
-                self._high = th.as_tensor(self.action_space.high.reshape(-1), dtype=th.float32, device=self.device)
-        return self
-
-    def set_training_mode(self, mode: bool) -> None:
-        self.training = bool(mode)
-
-    def train(self, mode: bool = True):
-        self.training = bool(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def _sync_transposed(self) -> None:
-        """(protocol of the MLP policies: nothing is shadowed here)"""
-
-    @property
-    def log_std(self) -> Optional[th.Tensor]:
-        return None if self.discrete else self._flat[: self.act_dim]
-
-    @property
-    def samples_on_host(self) -> bool:
-        """Discrete heads sample with torch.multinomial on the host (the reference's stream)."""
-        return self.discrete
-
-    @property
-    def squash_output(self) -> bool:
-        return False
-
-    def named_parameters(self) -> Iterator[Tuple[str, th.Tensor]]:
-        if not self.discrete:
-            yield "log_std", self._flat[: self.act_dim]
-        for i, name in enumerate(self._names):
-            yield f"{name}.weight", self._to_torch_layout(i, self.w(i)).reshape(self._shapes[i])
-            yield f"{name}.bias", self.b(i)
-
-    def parameters(self) -> Iterator[th.Tensor]:
-        for _, p in self.named_parameters():
-            yield p
-
-    def state_dict(self) -> Dict[str, th.Tensor]:
-        """SB3's keys: the shared extractor appears under three names."""
-        sd: Dict[str, th.Tensor] = {}
-        named = dict(self.named_parameters())
-        if not self.discrete:
-            sd["log_std"] = named.pop("log_std")
-        for alias in ("features_extractor", "pi_features_extractor", "vf_features_extractor"):
-            for k, v in named.items():
-                if k.startswith("features_extractor."):
-                    sd[alias + k[len("features_extractor"):]] = v
-        for k, v in named.items():
-            if not k.startswith("features_extractor."):
-                sd[k] = v
-        return sd
-
-    def load_state_dict(self, sd) -> None:
-        if not self.discrete:
-            self._flat[: self.act_dim].copy_(th.as_tensor(sd["log_std"]).to(self.device).float().reshape(-1))
-        for i, name in enumerate(self._names):
-            self.w(i).copy_(self._to_device_layout(i, th.as_tensor(sd[f"{name}.weight"]).to(self.device).float()).reshape(-1))
-            self.b(i).copy_(th.as_tensor(sd[f"{name}.bias"]).to(self.device).float().reshape(-1))
-
     # ---- forward / backward ----------------------------------------------------------------------------
+    def _head_buffers(self, B: int, d: Dict[str, th.Tensor]) -> None:
+        """The subclass's own batch buffers (head outputs and their gradients), added to `d`."""
+
     def _buffers(self, B: int) -> Dict[str, th.Tensor]:
         if B not in self._bufs:
             f = lambda *s: th.empty(*s, device=self.device)
@@ -254,13 +164,11 @@ class ActorCriticCnnPolicy:
                 else:
                     d[f"col{li}"] = f(B * oh * ow, cin * k * k)
                 d[f"act{li}"] = f(B * oh * ow, cout)           # channel-last [B, OH, OW, Cout], post-ReLU
-            d["feat"], d["logits"], d["values"] = f(B, self.features_dim), f(B, self.n_actions), f(B, 1)
-            d["logp"], d["ent"], d["acts"] = f(B), f(B), f(B, 1 if self.discrete else self.act_dim)
-            d["dlogits"], d["dfeat"], d["dflat"] = f(B, self.n_actions), f(B, self.features_dim), f(B, self.n_flatten)
+            d["feat"], d["dfeat"], d["dflat"] = f(B, self.features_dim), f(B, self.features_dim), f(B, self.n_flatten)
             for li in (1, 2):  # input gradients of conv 2 and 3 (conv 1's input is the image)
                 cin, h, w_, _, k, _, oh, ow = self.geom[li]
                 d[f"dact{li - 1}"] = f(B * h * w_, cin)      # (`dcol{li}` only exists on the explicit path: `_dcol`)
-            d["dvalues"], d["dhead"] = f(B, 1), f(2, B, self.features_dim)
+            self._head_buffers(B, d)
             if len(self._bufs) >= 3:   # rollout step, bootstrap chunk, minibatch: more sizes evict the oldest
                 self._bufs.pop(next(iter(self._bufs)))
             self._bufs[B] = d
@@ -270,8 +178,6 @@ class ActorCriticCnnPolicy:
     def _gemm(mode, A, lda, Bm, ldb, Cm, ldc, M, N, K, bias=None, act=0, P=None, ldp=0, splits=1, dbias=None):
         L.call("ia_gemm_f32", mode, L.ptr(A), lda, L.ptr(Bm), ldb, L.ptr(Cm), ldc, M, N, K, L.ptr(bias), act,
                L.ptr(P), ldp, splits, L.ptr(dbias), L.stream())
-
-    takes_uint8_frames = True   # (`PPO`: the rollout tile's host rows and their transfer are uint8 for this policy)
 
     # rows of a weight gradient's contraction per K split (<= 64 splits): a convolution's [64 x 512] gradient is 8 output tiles
     # -- at 2 048 rows per split a 256-frame minibatch (20 736 rows) ran on 80 workgroups of 64 K chunks each
@@ -297,8 +203,8 @@ class ActorCriticCnnPolicy:
             raise TypeError("image observations must be uint8 (the policy applies [SB3 preprocess_obs]: x / 255)")
         return t.to(self.device).reshape(-1, *self.observation_space.shape).contiguous()
 
-    def _forward(self, obs_u8: th.Tensor, values_out: Optional[th.Tensor] = None) -> Dict[str, th.Tensor]:
-        """`values_out` (contiguous [B] device row): the value head writes there instead of into the batch buffer."""
+    def _forward_trunk(self, obs_u8: th.Tensor) -> Dict[str, th.Tensor]:
+        """The batch buffers of `obs_u8`'s size with the activations and `feat` [B, features_dim] filled in."""
         require_device(self.device)
         B = obs_u8.shape[0]
         d = self._buffers(B)
@@ -334,35 +240,7 @@ class ActorCriticCnnPolicy:
         else:
             self._gemm(0, flat, self.n_flatten, self.w(3), self.n_flatten, d["feat"], self.features_dim, B,
                        self.features_dim, self.n_flatten, bias=self.b(3), act=1)
-        F_ = self.features_dim
-        self._gemm(0, d["feat"], F_, self.w(4), F_, d["logits"], self.n_actions, B, self.n_actions, F_, bias=self.b(4))
-        self._gemm(0, d["feat"], F_, self.w(5), F_, d["values"] if values_out is None else values_out, 1, B, 1, F_,
-                   bias=self.b(5))
         return d
-
-    def evaluate_actions(self, obs, actions, logp_coef: float = 0.0, ent_coef: float = 0.0, want_grad: bool = False):
-        """[SB3 evaluate_actions] -> (values [B,1], log_prob [B], entropy [B]). With `want_grad`, the gradient of
-        `logp_coef * sum(log_prob) + ent_coef * sum(entropy)` w.r.t. the logits is left for `backward()`."""
-        obs_u8 = self._obs_u8(obs)
-        d = self._forward(obs_u8)
-        B = obs_u8.shape[0]
-        a = actions if isinstance(actions, th.Tensor) else th.as_tensor(np.ascontiguousarray(actions))
-        d["acts"].copy_(a.to(self.device).reshape(d["acts"].shape).float())
-        if not self.discrete:
-            L.call("ia_gauss_eval", L.ptr(d["logits"]), L.ptr(self._flat), L.ptr(d["acts"]), B, self.act_dim,
-                   L.ptr(d["logp"]), L.ptr(d["ent"]), L.stream())
-            if want_grad:   # Gaussian head: the head-loss kernel forms the gradient (see `head_grad_of_coefficients`)
-                from imitation_amd.general_policy import head_grad_of_coefficients
-                hw = d.setdefault("bc_ws", {})
-                head_grad_of_coefficients(False, d["logits"], L.ptr(self._flat), d["values"], d["acts"], d["logp"], B,
-                                          self.act_dim, logp_coef, ent_coef, hw)
-                d["dlogits"].copy_(hw["d_out"])
-                d["dls_pending"] = hw["dls"]
-            return d["values"], d["logp"], d["ent"]
-        L.call("ia_categorical_loss", L.ptr(d["logits"]), self.n_actions, L.ptr(d["acts"]), B, self.n_actions,
-               float(logp_coef), float(ent_coef), L.ptr(d["logp"]), L.ptr(d["ent"]),
-               L.ptr(d["dlogits"]) if want_grad else None, L.stream())
-        return d["values"], d["logp"], d["ent"]
 
     def _wgrad(self, li: int, dout: th.Tensor, rows: int, n_out: int, inp: th.Tensor, K: int, grad: th.Tensor,
                im=None) -> None:
@@ -438,26 +316,11 @@ class ActorCriticCnnPolicy:
         L.call("ia_gemm_f32_im2col_pad", 0, L.ptr(dout), Kd, L.ptr(Wd_all), Kd, L.ptr(dact), cin, B * gh * gw, s * s * cin, Kd,
                None, 0, 1, None, oh, ow, cout, kt, kt, 1, kt - 1, cmap, L.ptr(d[f"act{li - 1}"]), L.stream())
 
-    def backward(self, B: int, grad: th.Tensor, with_values: bool = False) -> None:
-        """Adds to `grad` (flat, device layout) the parameter gradient of the loss whose head gradients were left in
-        the batch-`B` buffers: `dlogits` (by `evaluate_actions(..., want_grad=True)` or the PPO head loss) and, with
-        `with_values`, `dvalues` (PPO's value loss; the BC loss has no value term)."""
-        d = self._bufs[B]
-        F_, A = self.features_dim, self.n_actions
-        if d.get("dls_pending") is not None:   # log_std gradient of a Box-head BC step
-            L.call("ia_reduce_partials", L.ptr(d["dls_pending"]), 1, A, 1.0, 1, L.ptr(grad), L.stream())
-            d["dls_pending"] = None
-        self._wgrad(4, d["dlogits"], B, A, d["feat"], F_, grad)
-        if with_values:
-            self._wgrad(5, d["dvalues"], B, 1, d["feat"], F_, grad)
-            # d feat = relu'(feat) * (dlogits . Wa + dvalues . Wv): two NN GEMMs into one [2][B, F] slab pair,
-            # summed in slab order, then the ReLU mask
-            self._gemm(1, d["dlogits"], A, self.w(4), F_, d["dhead"][0], F_, B, F_, A)
-            self._gemm(1, d["dvalues"], 1, self.w(5), F_, d["dhead"][1], F_, B, F_, 1)
-            L.call("ia_reduce_partials", L.ptr(d["dhead"]), 2, B * F_, 1.0, 0, L.ptr(d["dhead"][0]), L.stream())
-            L.call("ia_relu_backward", L.ptr(d["dhead"][0]), L.ptr(d["feat"]), B * F_, L.ptr(d["dfeat"]), L.stream())
-        else:
-            self._gemm(1, d["dlogits"], A, self.w(4), F_, d["dfeat"], F_, B, F_, A, act=1, P=d["feat"], ldp=F_)
+    def _backward_trunk(self, B: int, d: Dict[str, th.Tensor], grad: th.Tensor) -> None:
+        """Adds to `grad` (flat, device layout) the gradient of the extractor's parameters from `d["dfeat"]` = d loss /
+        d feat (already masked by feat > 0), then the queued ordered sums of every weight-gradient slab (the heads'
+        `_wgrad` calls before this one included)."""
+        F_ = self.features_dim
         flat = d["act2"].view(B, self.n_flatten)
         self._wgrad(3, d["dfeat"], B, F_, flat, self.n_flatten, grad)
         self._gemm(1, d["dfeat"], F_, self.w(3), self.n_flatten, d["dflat"], self.n_flatten, B, self.n_flatten, F_,
@@ -485,6 +348,194 @@ class ActorCriticCnnPolicy:
                        L.ptr(d[f"dact{li - 1}"]), L.stream())
             dout = d[f"dact{li - 1}"]
         self._flush_reduces()
+
+
+class ActorCriticCnnPolicy(NatureCnnTrunk):
+    def __init__(self, observation_space, action_space, lr_schedule, net_arch=None, activation_fn=nn.Tanh,
+                 ortho_init: bool = True, use_sde: bool = False, log_std_init: float = 0.0,
+                 features_extractor_class=NatureCNN, features_extractor_kwargs=None, share_features_extractor: bool = True,
+                 normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs=None):
+        if not _is_image_space(observation_space):
+            raise ValueError("ActorCriticCnnPolicy is for uint8 image spaces [C, H, W] with bounds 0 / 255")
+        self.discrete = isinstance(action_space, spaces.Discrete)
+        if not self.discrete and not (isinstance(action_space, spaces.Box) and len(action_space.shape) == 1):
+            raise NotImplementedError("image policies implement Discrete (Categorical) and 1-D Box (DiagGaussian) heads")
+        if net_arch not in (None, [], {}):
+            raise NotImplementedError("hidden layers behind NatureCNN are not implemented (SB3's default is none)")
+        if features_extractor_class is not NatureCNN or not normalize_images:
+            raise NotImplementedError("only NatureCNN on [0, 255] frames is implemented")
+        self.action_space = action_space
+        self._init_trunk(observation_space, int((features_extractor_kwargs or {}).get("features_dim", 512)))
+        self.features_extractor = NatureCNN(observation_space, self.features_dim)
+        self.act_dim = int(action_space.n) if self.discrete else int(action_space.shape[0])
+        self.n_actions = self.act_dim               # width of the action head (logits or Gaussian means)
+        self.fused = False                          # PPO runs this policy's own minibatch loop (`ppo_update`)
+        self.discrete_sampling = "multinomial"
+        self.training = True
+        self.optimizer_kwargs = dict(optimizer_kwargs or {})
+        self.optimizer_kwargs.setdefault("eps", 1e-5)   # SB3 ActorCriticPolicy default for Adam
+        self.optimizer = None
+        self._low = self._high = None
+        if optimizer_class is not th.optim.Adam:
+            raise NotImplementedError("the PPO step implements Adam (SB3 default)")
+        # Host construction in SB3's order so that torch's global generator is consumed identically:
+        # the three convolutions, the linear layer, action_net, value_net; then orthogonal re-initialisation
+        # (features extractor sqrt(2), action_net 0.01, value_net 1).
+        cnn, linear = self._host_trunk()
+        action_net = nn.Linear(self.features_dim, self.n_actions)
+        log_std = None if self.discrete else th.ones(self.act_dim) * log_std_init
+        value_net = nn.Linear(self.features_dim, 1)
+        if ortho_init:
+            def init(m, gain):
+                if isinstance(m, (nn.Linear, nn.Conv2d)):
+                    nn.init.orthogonal_(m.weight, gain=gain)
+                    m.bias.data.fill_(0.0)
+            for mod, gain in ((cnn, np.sqrt(2)), (linear, np.sqrt(2)), (action_net, 0.01), (value_net, 1)):
+                mod.apply(functools.partial(init, gain=gain))
+        # torch `parameters()` order: the policy's own parameter (log_std, Box heads) first, then the child modules
+        self._set_flat(["features_extractor.cnn.0", "features_extractor.cnn.2", "features_extractor.cnn.4",
+                        "features_extractor.linear.0", "action_net", "value_net"],
+                       [cnn[0], cnn[2], cnn[4], linear[0], action_net, value_net], [] if self.discrete else [log_std])
+        self._lr0 = float(lr_schedule(1))
+
+    def to(self, device):
+        from imitation_amd.networks import HipAdam
+        self.device = th.device(device)
+        self._flat = self._flat.to(self.device).contiguous()
+        if self.device.type == "cuda":
+            self._resolve_conv1()
+            self.optimizer = HipAdam(self._flat, th.zeros_like(self._flat), lr=self._lr0, **self.optimizer_kwargs)
+            if self.discrete:
+                self._low = self._high = th.zeros(self.act_dim, device=self.device)
+            else:
+                self._low = th.as_tensor(self.action_space.low.reshape(-1), dtype=th.float32, device=self.device)
+                self._high = th.as_tensor(self.action_space.high.reshape(-1), dtype=th.float32, device=self.device)
+        return self
+
+    def set_training_mode(self, mode: bool) -> None:
+        self.training = bool(mode)
+
+    def train(self, mode: bool = True):
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def _sync_transposed(self) -> None:
+        """(protocol of the MLP policies: nothing is shadowed here)"""
+
+    @property
+    def log_std(self) -> Optional[th.Tensor]:
+        return None if self.discrete else self._flat[: self.act_dim]
+
+    @property
+    def samples_on_host(self) -> bool:
+        """Discrete heads sample with torch.multinomial on the host (the reference's stream)."""
+        return self.discrete
+
+    @property
+    def squash_output(self) -> bool:
+        return False
+
+    def named_parameters(self) -> Iterator[Tuple[str, th.Tensor]]:
+        if not self.discrete:
+            yield "log_std", self._flat[: self.act_dim]
+        for i, name in enumerate(self._names):
+            yield f"{name}.weight", self._to_torch_layout(i, self.w(i)).reshape(self._shapes[i])
+            yield f"{name}.bias", self.b(i)
+
+    def parameters(self) -> Iterator[th.Tensor]:
+        for _, p in self.named_parameters():
+            yield p
+
+    def state_dict(self) -> Dict[str, th.Tensor]:
+        """SB3's keys: the shared extractor appears under three names."""
+        sd: Dict[str, th.Tensor] = {}
+        named = dict(self.named_parameters())
+        if not self.discrete:
+            sd["log_std"] = named.pop("log_std")
+        for alias in ("features_extractor", "pi_features_extractor", "vf_features_extractor"):
+            for k, v in named.items():
+                if k.startswith("features_extractor."):
+                    sd[alias + k[len("features_extractor"):]] = v
+        for k, v in named.items():
+            if not k.startswith("features_extractor."):
+                sd[k] = v
+        return sd
+
+    def load_state_dict(self, sd) -> None:
+        if not self.discrete:
+            self._flat[: self.act_dim].copy_(th.as_tensor(sd["log_std"]).to(self.device).float().reshape(-1))
+        for i, name in enumerate(self._names):
+            self.w(i).copy_(self._to_device_layout(i, th.as_tensor(sd[f"{name}.weight"]).to(self.device).float()).reshape(-1))
+            self.b(i).copy_(th.as_tensor(sd[f"{name}.bias"]).to(self.device).float().reshape(-1))
+
+    takes_uint8_frames = True   # (`PPO`: the rollout tile's host rows and their transfer are uint8 for this policy)
+
+    # ---- forward / backward: the heads around the trunk ------------------------------------------------------
+    def _head_buffers(self, B: int, d: Dict[str, th.Tensor]) -> None:
+        f = lambda *s: th.empty(*s, device=self.device)
+        d["logits"], d["values"] = f(B, self.n_actions), f(B, 1)
+        d["logp"], d["ent"], d["acts"] = f(B), f(B), f(B, 1 if self.discrete else self.act_dim)
+        d["dlogits"] = f(B, self.n_actions)
+        d["dvalues"], d["dhead"] = f(B, 1), f(2, B, self.features_dim)
+
+    def _forward(self, obs_u8: th.Tensor, values_out: Optional[th.Tensor] = None) -> Dict[str, th.Tensor]:
+        """`values_out` (contiguous [B] device row): the value head writes there instead of into the batch buffer."""
+        d = self._forward_trunk(obs_u8)
+        B = obs_u8.shape[0]
+        F_ = self.features_dim
+        self._gemm(0, d["feat"], F_, self.w(4), F_, d["logits"], self.n_actions, B, self.n_actions, F_, bias=self.b(4))
+        self._gemm(0, d["feat"], F_, self.w(5), F_, d["values"] if values_out is None else values_out, 1, B, 1, F_,
+                   bias=self.b(5))
+        return d
+
+    def evaluate_actions(self, obs, actions, logp_coef: float = 0.0, ent_coef: float = 0.0, want_grad: bool = False):
+        """[SB3 evaluate_actions] -> (values [B,1], log_prob [B], entropy [B]). With `want_grad`, the gradient of
+        `logp_coef * sum(log_prob) + ent_coef * sum(entropy)` w.r.t. the logits is left for `backward()`."""
+        obs_u8 = self._obs_u8(obs)
+        d = self._forward(obs_u8)
+        B = obs_u8.shape[0]
+        a = actions if isinstance(actions, th.Tensor) else th.as_tensor(np.ascontiguousarray(actions))
+        d["acts"].copy_(a.to(self.device).reshape(d["acts"].shape).float())
+        if not self.discrete:
+            L.call("ia_gauss_eval", L.ptr(d["logits"]), L.ptr(self._flat), L.ptr(d["acts"]), B, self.act_dim,
+                   L.ptr(d["logp"]), L.ptr(d["ent"]), L.stream())
+            if want_grad:   # Gaussian head: the head-loss kernel forms the gradient (see `head_grad_of_coefficients`)
+                from imitation_amd.general_policy import head_grad_of_coefficients
+                hw = d.setdefault("bc_ws", {})
+                head_grad_of_coefficients(False, d["logits"], L.ptr(self._flat), d["values"], d["acts"], d["logp"], B,
+                                          self.act_dim, logp_coef, ent_coef, hw)
+                d["dlogits"].copy_(hw["d_out"])
+                d["dls_pending"] = hw["dls"]
+            return d["values"], d["logp"], d["ent"]
+        L.call("ia_categorical_loss", L.ptr(d["logits"]), self.n_actions, L.ptr(d["acts"]), B, self.n_actions,
+               float(logp_coef), float(ent_coef), L.ptr(d["logp"]), L.ptr(d["ent"]),
+               L.ptr(d["dlogits"]) if want_grad else None, L.stream())
+        return d["values"], d["logp"], d["ent"]
+
+    def backward(self, B: int, grad: th.Tensor, with_values: bool = False) -> None:
+        """Adds to `grad` (flat, device layout) the parameter gradient of the loss whose head gradients were left in
+        the batch-`B` buffers: `dlogits` (by `evaluate_actions(..., want_grad=True)` or the PPO head loss) and, with
+        `with_values`, `dvalues` (PPO's value loss; the BC loss has no value term)."""
+        d = self._bufs[B]
+        F_, A = self.features_dim, self.n_actions
+        if d.get("dls_pending") is not None:   # log_std gradient of a Box-head BC step
+            L.call("ia_reduce_partials", L.ptr(d["dls_pending"]), 1, A, 1.0, 1, L.ptr(grad), L.stream())
+            d["dls_pending"] = None
+        self._wgrad(4, d["dlogits"], B, A, d["feat"], F_, grad)
+        if with_values:
+            self._wgrad(5, d["dvalues"], B, 1, d["feat"], F_, grad)
+            # d feat = relu'(feat) * (dlogits . Wa + dvalues . Wv): two NN GEMMs into one [2][B, F] slab pair,
+            # summed in slab order, then the ReLU mask
+            self._gemm(1, d["dlogits"], A, self.w(4), F_, d["dhead"][0], F_, B, F_, A)
+            self._gemm(1, d["dvalues"], 1, self.w(5), F_, d["dhead"][1], F_, B, F_, 1)
+            L.call("ia_reduce_partials", L.ptr(d["dhead"]), 2, B * F_, 1.0, 0, L.ptr(d["dhead"][0]), L.stream())
+            L.call("ia_relu_backward", L.ptr(d["dhead"][0]), L.ptr(d["feat"]), B * F_, L.ptr(d["dfeat"]), L.stream())
+        else:
+            self._gemm(1, d["dlogits"], A, self.w(4), F_, d["dfeat"], F_, B, F_, A, act=1, P=d["feat"], ldp=F_)
+        self._backward_trunk(B, d, grad)
 
     # ---- PPO generator protocol (the surface `ppo.PPO` and the adversarial trainer drive; same as
     # `general_policy.GeneralTowers`) ---------------------------------------------------------------------------

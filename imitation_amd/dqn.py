@@ -11,6 +11,10 @@ The update itself is `ia_dqn_update` (csrc/dqn.hip): all gradient steps of a `tr
 for `net_arch=[H, H]`, H in {32, 64}, ReLU, D <= 64, A <= 16, batch <= 256. Every other Q-net runs the same update from
 the general kernels (`ia_gather_rows`, `ia_mlp_forward` twice, `ia_dqn_td_loss`, `ia_mlp_backward` + `ia_reduce_partials`,
 `ia_clip_grad_norm`, `ia_dqn_adam_step`); `IA_DQN_FUSED=0` in the environment forces that path (tests, tools).
+
+Image observations ("CnnPolicy"): `CnnQNetwork` is SB3's `QNetwork` over `NatureCNN` on the trunk of
+`cnn_policy.NatureCnnTrunk`; the ring and the expert table of an image space hold uint8 frames, and the update's third
+route, `DQNPolicy.update_frames`, assembles each step's minibatch with one `ia_dqn_assemble_u8` launch (csrc/dqn_frames.hip).
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ from torch import nn
 from imitation_amd import _lib as L
 from imitation_amd import logger as imit_logger
 from imitation_amd import spaces
+from imitation_amd.cnn_policy import NatureCNN, NatureCnnTrunk, _is_image_space
 from imitation_amd.networks import require_device
 from imitation_amd.policies import FlattenExtractor
 from imitation_amd.ppo import _CallbackList, _NullCallback, _schedule, set_random_seed
@@ -99,13 +104,16 @@ class ReplayIndex:
 
 
 class _Table:
-    """Flat device table of transitions: obs / next_obs [N, D] float32, action int64 [N] (Discrete) or float32 [N, A]
+    """Flat device table of transitions: obs / next_obs [N, D] float32 -- or uint8 for an image space (`frames`: D = C*H*W
+    bytes per row, the frames as the environment hands them over) --, action int64 [N] (Discrete) or float32 [N, A]
     (Box, `act_dim` = A), reward, done float32 [N]."""
 
-    def __init__(self, rows: int, obs_dim: int, device, act_dim: Optional[int] = None):
-        self.rows, self.obs_dim, self.act_dim = int(rows), int(obs_dim), act_dim
-        self.obs = th.zeros(self.rows, obs_dim, device=device)
-        self.next_obs = th.zeros(self.rows, obs_dim, device=device)
+    def __init__(self, rows: int, obs_dim: int, device, act_dim: Optional[int] = None, frames: bool = False):
+        self.rows, self.obs_dim, self.act_dim, self.frames = int(rows), int(obs_dim), act_dim, bool(frames)
+        self.obs_np = np.uint8 if self.frames else np.float32
+        obs_dtype = th.uint8 if self.frames else th.float32
+        self.obs = th.zeros(self.rows, obs_dim, dtype=obs_dtype, device=device)
+        self.next_obs = th.zeros(self.rows, obs_dim, dtype=obs_dtype, device=device)
         if act_dim is None:
             self.action = th.zeros(self.rows, dtype=th.int64, device=device)
         else:
@@ -116,7 +124,9 @@ class _Table:
     def write(self, lo: int, obs, next_obs, action, reward, done) -> None:
         n = len(obs)
         act = (np.int64, (n,)) if self.act_dim is None else (np.float32, (n, self.act_dim))
-        for dst, src, dtype, shape in ((self.obs, obs, np.float32, (n, -1)), (self.next_obs, next_obs, np.float32, (n, -1)),
+        if self.frames and not (np.asarray(obs).dtype == np.uint8 and np.asarray(next_obs).dtype == np.uint8):
+            raise ValueError("a frame table stores uint8 frames as they come: the observations must be uint8 arrays")
+        for dst, src, dtype, shape in ((self.obs, obs, self.obs_np, (n, -1)), (self.next_obs, next_obs, self.obs_np, (n, -1)),
                                        (self.action, action) + act, (self.reward, reward, np.float32, (n,)),
                                        (self.done, done, np.float32, (n,))):
             dst[lo:lo + n].copy_(th.from_numpy(np.array(src, dtype).reshape(shape)))
@@ -127,7 +137,8 @@ def _device(device) -> th.device:
 
 
 class ReplayBuffer:
-    """[SB3 buffers.ReplayBuffer] for flat Box observations and Discrete or flat Box actions, its rows in device memory.
+    """[SB3 buffers.ReplayBuffer] for flat Box observations (float32 rows) or uint8 image observations (uint8 rows of
+    C*H*W bytes, `frames`) and Discrete or flat Box actions, its rows in device memory.
     `handle_timeout_termination`: a `done` that is a time-limit truncation does not cut the bootstrap (the product
     `done * (1 - timeout)` SB3 forms when sampling is formed when the row is stored)."""
 
@@ -146,7 +157,9 @@ class ReplayBuffer:
         self.index = ReplayIndex(buffer_size, n_envs)
         self.buffer_size = self.index.buffer_size
         self.handle_timeout_termination = handle_timeout_termination
-        self.table = _Table(self.buffer_size * self.n_envs, self.obs_dim, self.device, self.act_dim)
+        # an image space's frames stay uint8 end to end: uint8 [rows, C*H*W] tables, no float round trip
+        self.frames = _is_image_space(observation_space)
+        self.table = _Table(self.buffer_size * self.n_envs, self.obs_dim, self.device, self.act_dim, frames=self.frames)
         # `RewardStepSource`: `add` then ignores its `reward` and stores the step with one `ia_offpolicy_step` launch
         self.reward_source: Optional["RewardStepSource"] = None
 
@@ -183,7 +196,11 @@ class ReplayBuffer:
 
     def _gather(self, table: _Table, rows: np.ndarray) -> ReplayBufferSamples:
         idx = th.from_numpy(rows).to(self.device)
-        return ReplayBufferSamples(table.obs[idx], table.action[idx].reshape(-1, table.act_dim or 1), table.next_obs[idx],
+        obs, next_obs = table.obs[idx], table.next_obs[idx]
+        if self.frames:   # (uint8 [b, C, H, W], as SB3's buffer returns them)
+            shape = (-1,) + tuple(self.observation_space.shape)
+            obs, next_obs = obs.reshape(shape), next_obs.reshape(shape)
+        return ReplayBufferSamples(obs, table.action[idx].reshape(-1, table.act_dim or 1), next_obs,
                                    table.done[idx].reshape(-1, 1), table.reward[idx].reshape(-1, 1))
 
     def sample(self, batch_size: int, env=None) -> ReplayBufferSamples:
@@ -210,6 +227,9 @@ class RewardStepSource:
     SLOTS = 8
 
     def __init__(self, ring: "ReplayBuffer", reward_net, slots: Optional[int] = None, tile_steps: int = 64):
+        if ring.frames:
+            raise NotImplementedError("a learned reward on a uint8 frame ring is not implemented (ia_offpolicy_step reads "
+                                      "and writes float32 rows)")
         self.ring, self.net = ring, reward_net
         self.device = ring.device
         self.n, self.od = ring.n_envs, ring.obs_dim
@@ -448,6 +468,87 @@ class QNetwork:
         return q, None
 
 
+class CnnQNetwork(NatureCnnTrunk):
+    """[SB3 dqn.policies.QNetwork] over `NatureCNN(features_dim)` with SB3's default `net_arch=[]` behind it: `q_net` is
+    one `Linear(features_dim, n_actions)`. Torch's default initialisation (DQN does no orthogonal re-init), modules built
+    on the host in SB3's order (conv 0 / 2 / 4, linear.0, the head). Parameters: one flat fp32 buffer in the trunk's device
+    layout (`cnn_policy.NatureCnnTrunk`); `state_dict` / `load_state_dict` permute to and from torch's layouts."""
+
+    def __init__(self, observation_space, action_space, features_dim: int = 512):
+        if not isinstance(action_space, spaces.Discrete):
+            raise NotImplementedError("DQN needs a Discrete action space")
+        if not _is_image_space(observation_space):
+            raise ValueError("the CNN Q-network is for uint8 image spaces [C, H, W] with bounds 0 / 255")
+        self.action_space = action_space
+        self.n_actions = int(action_space.n)
+        self.net_arch: List[int] = []
+        self._init_trunk(observation_space, features_dim)
+        cnn, linear = self._host_trunk()
+        head = nn.Linear(self.features_dim, self.n_actions)
+        self._set_flat(["features_extractor.cnn.0", "features_extractor.cnn.2", "features_extractor.cnn.4",
+                        "features_extractor.linear.0", "q_net.0"], [cnn[0], cnn[2], cnn[4], linear[0], head], [])
+
+    def to(self, device):
+        self.device = th.device(device)
+        self._flat = self._flat.to(self.device).contiguous()
+        self._bufs, self._dgrad_idx = {}, {}
+        if self.device.type == "cuda":
+            self._resolve_conv1()
+        return self
+
+    def fused_shape(self) -> bool:
+        return False
+
+    def named_parameters(self):
+        for i, name in enumerate(self._names):
+            yield f"{name}.weight", self._to_torch_layout(i, self.w(i)).reshape(self._shapes[i])
+            yield f"{name}.bias", self.b(i)
+
+    def parameters(self):
+        for _, p in self.named_parameters():
+            yield p
+
+    def state_dict(self) -> Dict[str, th.Tensor]:
+        return dict(self.named_parameters())
+
+    def load_state_dict(self, sd) -> None:
+        for i, name in enumerate(self._names):
+            w = th.as_tensor(sd[f"{name}.weight"]).to(self.device).float().reshape(self._shapes[i])
+            self.w(i).copy_(self._to_device_layout(i, w).reshape(-1))
+            self.b(i).copy_(th.as_tensor(sd[f"{name}.bias"]).to(self.device).float().reshape(-1))
+
+    def grad_to_torch(self, grad: th.Tensor) -> Dict[str, th.Tensor]:
+        """A flat vector in the parameters' device layout (a gradient, an Adam moment) under `state_dict`'s keys and
+        layouts."""
+        out = {}
+        for i, name in enumerate(self._names):
+            ow, nw, ob, nb = self._offsets[i]
+            out[f"{name}.weight"] = self._to_torch_layout(i, grad[ow:ow + nw]).reshape(self._shapes[i])
+            out[f"{name}.bias"] = grad[ob:ob + nb]
+        return out
+
+    def _head_buffers(self, B: int, d: Dict[str, th.Tensor]) -> None:
+        d["q"] = th.empty(B, self.n_actions, device=self.device)
+        d["dq"] = th.empty(B, self.n_actions, device=self.device)
+
+    def forward(self, obs_u8: th.Tensor) -> Dict[str, th.Tensor]:
+        """The batch buffers with `q` [B, A] = Q(obs, .) of device frames `obs_u8` uint8 [B, C, H, W] (and the activations
+        `backward` needs)."""
+        d = self._forward_trunk(obs_u8)
+        F_, A = self.features_dim, self.n_actions
+        self._gemm(0, d["feat"], F_, self.w(4), F_, d["q"], A, obs_u8.shape[0], A, F_, bias=self.b(4))
+        return d
+
+    def backward(self, B: int, grad: th.Tensor) -> None:
+        """Adds to `grad` (flat, device layout) the parameter gradient of the loss whose gradient w.r.t. Q the caller left
+        in the batch-`B` buffers' `dq`."""
+        d = self._bufs[B]
+        F_, A = self.features_dim, self.n_actions
+        self._wgrad(4, d["dq"], B, A, d["feat"], F_, grad)
+        self._gemm(1, d["dq"], A, self.w(4), F_, d["dfeat"], F_, B, F_, A, act=1, P=d["feat"], ldp=F_)
+        self._backward_trunk(B, d, grad)
+
+
 class DQNPolicy:
     """[SB3 dqn.policies.DQNPolicy]: `q_net`, then a separately initialised `q_net_target` that loads the online
     net's state, then Adam over the online parameters."""
@@ -455,19 +556,39 @@ class DQNPolicy:
     def __init__(self, observation_space, action_space, lr_schedule, net_arch: Optional[List[int]] = None,
                  activation_fn=nn.ReLU, features_extractor_class=FlattenExtractor, features_extractor_kwargs=None,
                  normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs=None):
-        if features_extractor_class is not FlattenExtractor:
-            raise NotImplementedError("only the flatten extractor (MlpPolicy) is implemented")
+        if features_extractor_class not in (FlattenExtractor, NatureCNN):
+            raise NotImplementedError("only the flatten extractor (MlpPolicy) and NatureCNN (CnnPolicy) are implemented")
         if optimizer_class is not th.optim.Adam:
             raise NotImplementedError("only torch.optim.Adam is implemented")
         self.observation_space, self.action_space = observation_space, action_space
-        self.net_arch = [64, 64] if net_arch is None else list(net_arch)
+        # image policy: NatureCNN over uint8 frames, the update's third route (`update_frames`)
+        self.frames = features_extractor_class is NatureCNN
+        if self.frames:
+            if not _is_image_space(observation_space):
+                raise ValueError("CnnPolicy is for uint8 image spaces [C, H, W] with bounds 0 / 255")
+            if int(np.argmin(observation_space.shape)) != 0:
+                raise NotImplementedError("channel-last image spaces are not implemented (there is no VecTransposeImage "
+                                          "here): pass frames as [C, H, W]")
+            if not normalize_images:
+                raise NotImplementedError("normalize_images=False is not implemented: the first layer scales by 1 / 255")
+            if net_arch not in (None, []):
+                raise NotImplementedError("hidden layers behind NatureCNN are not implemented (SB3's CnnPolicy has none)")
+            unknown = set(features_extractor_kwargs or {}) - {"features_dim"}
+            if unknown:
+                raise NotImplementedError(f"features_extractor_kwargs {sorted(unknown)} are not implemented")
+        self.net_arch = [] if self.frames else [64, 64] if net_arch is None else list(net_arch)
         self.activation_fn = activation_fn
         self.optimizer_kwargs = dict(optimizer_kwargs or {})
         unknown = set(self.optimizer_kwargs) - {"betas", "eps", "weight_decay"}
         if unknown:
             raise NotImplementedError(f"optimizer_kwargs {sorted(unknown)} are not implemented")
-        self.q_net = QNetwork(observation_space, action_space, self.net_arch, activation_fn)
-        self.q_net_target = QNetwork(observation_space, action_space, self.net_arch, activation_fn)
+        if self.frames:
+            features_dim = int((features_extractor_kwargs or {}).get("features_dim", 512))
+            self.q_net = CnnQNetwork(observation_space, action_space, features_dim)
+            self.q_net_target = CnnQNetwork(observation_space, action_space, features_dim)
+        else:
+            self.q_net = QNetwork(observation_space, action_space, self.net_arch, activation_fn)
+            self.q_net_target = QNetwork(observation_space, action_space, self.net_arch, activation_fn)
         self.q_net_target._flat.copy_(self.q_net._flat)
         self.lr = float(lr_schedule(1))
         self.betas = tuple(self.optimizer_kwargs.get("betas", (0.9, 0.999)))
@@ -509,6 +630,13 @@ class DQNPolicy:
 
     def q_values(self, observation: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """Q and the greedy action of host observations (one upload, one read-back)."""
+        if self.frames:   # the uint8 frames go up as they are; the arg-max is the first maximum, taken on the host
+            frames = np.ascontiguousarray(observation)
+            if frames.dtype != np.uint8:
+                raise TypeError("image observations must be uint8 (the policy applies [SB3 preprocess_obs]: x / 255)")
+            frames = frames.reshape((-1,) + tuple(self.observation_space.shape))
+            qh = self.q_net.forward(th.from_numpy(frames).to(self.device))["q"].cpu().numpy()
+            return qh, qh.argmax(axis=1).astype(np.int64)
         obs = np.ascontiguousarray(observation, np.float32).reshape(-1, self.q_net.obs_dim)
         q, am = self.q_net.q_values(th.from_numpy(obs).to(self.device))
         if am is None:
@@ -632,15 +760,96 @@ class DQNPolicy:
             grad_out.copy_(w["grads"])
         self.adam_steps += n_steps
 
+    def _frames_ws(self, B: int):
+        key = ("frames", B)
+        if key not in self._ws:
+            q, dev = self.q_net, self.device
+            n = q._flat.numel()
+            self._ws[key] = dict(
+                obs=th.empty(B, q.obs_dim, dtype=th.uint8, device=dev), nxt=th.empty(B, q.obs_dim, dtype=th.uint8, device=dev),
+                act=th.empty(B, dtype=th.int64, device=dev), rew=th.empty(B, device=dev), done=th.empty(B, device=dev),
+                terms=th.empty(B, device=dev), grads=th.empty(n, device=dev),
+                clip_ws=th.empty(int(L.load().ia_clip_grad_norm_ws_floats()), device=dev))
+        return self._ws[key]
+
+    @staticmethod
+    def check_rows(rows: np.ndarray, n_new: int, ring: _Table, expert: Optional[_Table]) -> None:
+        """Every sampled row of a `train` call against its table's row count, on the host, before anything is launched
+        (`ia_dqn_assemble_u8` moves whole frames by these indices)."""
+        rows = np.asarray(rows).reshape(len(rows), -1)
+        for part, table, what in ((rows[:, :n_new], ring, "learner ring"), (rows[:, n_new:], expert, "expert table")):
+            if part.size == 0:
+                continue
+            if table is None:
+                raise ValueError(f"rows are drawn from the {what}, which does not exist")
+            if int(part.min()) < 0 or int(part.max()) >= table.rows:
+                raise IndexError(f"a sampled row lies outside the {what} ({table.rows} rows)")
+
+    def update_frames(self, ring: _Table, expert: Optional[_Table], idx_dev: th.Tensor, n_new: int, n_steps: int,
+                      batch_size: int, gamma: float, max_grad_norm: float, lr: float, stats: th.Tensor,
+                      grad_out: Optional[th.Tensor] = None) -> None:
+        """The steps of an image policy, per step: one `ia_dqn_assemble_u8` launch (the minibatch from the two uint8 frame
+        tables), the online trunk's forward on `obs`, the target trunk's on `next_obs`, `ia_dqn_td_loss`, the trunk's
+        backward seeded with `dq` into a flat gradient, `ia_clip_grad_norm`, `ia_dqn_adam_step`. The caller has checked the
+        rows against the tables (`check_rows`)."""
+        require_device(self.device)
+        if not (ring.frames and (expert is None or expert.frames)):
+            raise TypeError("update_frames reads uint8 frame tables")
+        q, qt, B, st = self.q_net, self.q_net_target, int(batch_size), L.stream()
+        w = self._frames_ws(B)
+        scal = self._adam_scalars(lr, n_steps)
+        n, D, e = q._flat.numel(), q.obs_dim, expert
+        shape = (B,) + tuple(self.observation_space.shape)
+        obs, nxt = w["obs"].view(shape), w["nxt"].view(shape)
+        idx_ptr, stats_ptr = idx_dev.data_ptr(), stats.data_ptr()
+        for s in range(n_steps):
+            L.call("ia_dqn_assemble_u8", L.ptr(ring.obs), L.ptr(ring.next_obs), L.ptr(ring.action), L.ptr(ring.reward),
+                   L.ptr(ring.done), ring.rows, None if e is None else L.ptr(e.obs), None if e is None else L.ptr(e.next_obs),
+                   None if e is None else L.ptr(e.action), None if e is None else L.ptr(e.reward),
+                   None if e is None else L.ptr(e.done), 0 if e is None else e.rows, idx_ptr + 8 * s * B, B, int(n_new), D,
+                   L.ptr(w["obs"]), L.ptr(w["nxt"]), L.ptr(w["act"]), L.ptr(w["rew"]), L.ptr(w["done"]), st)
+            d = q.forward(obs)
+            dt = qt.forward(nxt)
+            L.call("ia_dqn_td_loss", L.ptr(d["q"]), L.ptr(dt["q"]), L.ptr(w["act"]), L.ptr(w["rew"]), L.ptr(w["done"]), B,
+                   q.n_actions, float(gamma), L.ptr(d["dq"]), L.ptr(w["terms"]), stats_ptr + 8 * s, st)
+            w["grads"].zero_()
+            q.backward(B, w["grads"])
+            L.call("ia_clip_grad_norm", L.ptr(w["grads"]), n, float(max_grad_norm), stats_ptr + 8 * s + 4, L.ptr(w["clip_ws"]),
+                   st)
+            L.call("ia_dqn_adam_step", L.ptr(q._flat), L.ptr(w["grads"]), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), n,
+                   float(self.betas[0]), float(self.betas[1]), self.eps, self.weight_decay, float(scal[s, 0]),
+                   float(scal[s, 1]), st)
+        if grad_out is not None:
+            grad_out.copy_(w["grads"])
+        self.adam_steps += n_steps
+
     def update(self, ring: _Table, expert: Optional[_Table], idx_dev: th.Tensor, n_new: int, n_steps: int,
                batch_size: int, gamma: float, max_grad_norm: float, lr: float, stats: th.Tensor,
                grad_out: Optional[th.Tensor] = None) -> None:
-        """The fused launch where `fused_ok(batch_size)`, else the general path."""
+        """`update_frames` for an image policy; else the fused launch where `fused_ok(batch_size)`, else the general
+        path."""
+        if self.frames:
+            return self.update_frames(ring, expert, idx_dev, n_new, n_steps, batch_size, gamma, max_grad_norm, lr, stats,
+                                      grad_out)
+        if getattr(ring, "frames", False):
+            raise NotImplementedError("MlpPolicy on a uint8 frame ring is not implemented: use 'CnnPolicy'")
         fn = self.update_fused if self.fused_ok(batch_size) else self.update_general
         fn(ring, expert, idx_dev, n_new, n_steps, batch_size, gamma, max_grad_norm, lr, stats, grad_out)
 
 
 MlpPolicy = DQNPolicy
+
+
+class CnnPolicy(DQNPolicy):
+    """[SB3 dqn.policies.CnnPolicy]: `DQNPolicy` with `NatureCNN` as the features extractor, on uint8 [C, H, W] frames."""
+
+    def __init__(self, observation_space, action_space, lr_schedule, net_arch: Optional[List[int]] = None,
+                 activation_fn=nn.ReLU, features_extractor_class=NatureCNN, features_extractor_kwargs=None,
+                 normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs=None):
+        if features_extractor_class is FlattenExtractor:
+            raise NotImplementedError("CnnPolicy runs NatureCNN; the flatten extractor is MlpPolicy's")
+        super().__init__(observation_space, action_space, lr_schedule, net_arch, activation_fn, features_extractor_class,
+                         features_extractor_kwargs, normalize_images, optimizer_class, optimizer_kwargs)
 
 
 class OffPolicyAlgorithm:
@@ -801,7 +1010,7 @@ class OffPolicyAlgorithm:
 class DQN(OffPolicyAlgorithm):
     """[SB3 dqn.DQN] with `train_freq` in steps."""
 
-    policy_aliases = {"MlpPolicy": DQNPolicy}
+    policy_aliases = {"MlpPolicy": DQNPolicy, "CnnPolicy": CnnPolicy}
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size: int = 1_000_000, learning_starts: int = 50_000,
                  batch_size: int = 32, tau: float = 1.0, gamma: float = 0.99, train_freq=4, gradient_steps: int = 1,
@@ -813,7 +1022,7 @@ class DQN(OffPolicyAlgorithm):
                  seed: Optional[int] = None, device="auto", _init_setup_model: bool = True):
         if isinstance(policy, str):
             if policy not in self.policy_aliases:
-                raise NotImplementedError(f"policy {policy!r}: only 'MlpPolicy' is implemented for DQN")
+                raise NotImplementedError(f"policy {policy!r}: only 'MlpPolicy' and 'CnnPolicy' are implemented for DQN")
             policy = self.policy_aliases[policy]
         if isinstance(train_freq, tuple):
             if len(train_freq) != 2 or train_freq[1] != "step":
@@ -920,6 +1129,8 @@ class DQN(OffPolicyAlgorithm):
         for s in range(gradient_steps):
             rows[s], n_new = self.replay_buffer.sample_rows(batch_size)
         self.last_sample_rows, self.last_n_new = rows, n_new
+        if self.policy.frames:   # (the assemble kernel moves whole frames by these indices: checked before any launch)
+            self.policy.check_rows(rows, n_new, self.replay_buffer.table, self.replay_buffer.expert_table())
         idx_dev = th.from_numpy(rows).to(self.device)
         stats = th.empty(gradient_steps, 2, device=self.device)
         self._run_updates(rows, idx_dev, lambda lo, hi: self.policy.update(

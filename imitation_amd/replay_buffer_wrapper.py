@@ -30,6 +30,7 @@ import numpy as np
 import torch as th
 
 from imitation_amd import _lib as L
+from imitation_amd.cnn_policy import _is_image_space
 from imitation_amd.dqn import ReplayBuffer, ReplayBufferSamples, _Table
 from imitation_amd.networks import RunningNorm
 from imitation_amd.reward_nets import BasicRewardNet, NormalizedRewardNet, PredictProcessedWrapper, RewardNet
@@ -82,7 +83,7 @@ class _TableView:
     """A `_Table`-shaped view of the inner table whose `.reward` is the wrapper's relabelled column."""
 
     def __init__(self, inner: _Table, reward: th.Tensor):
-        self.rows, self.obs_dim, self.act_dim = inner.rows, inner.obs_dim, inner.act_dim
+        self.rows, self.obs_dim, self.act_dim, self.frames = inner.rows, inner.obs_dim, inner.act_dim, inner.frames
         self.obs, self.next_obs, self.action, self.done = inner.obs, inner.next_obs, inner.action, inner.done
         self.reward = reward
 
@@ -93,6 +94,10 @@ class ReplayBufferRewardWrapper(ReplayBuffer):
     def __init__(self, buffer_size: int, observation_space, action_space, *, replay_buffer_class, reward_fn: Callable,
                  **kwargs):
         assert replay_buffer_class is ReplayBuffer, "only ReplayBuffer is supported"
+        if _is_image_space(observation_space):
+            raise NotImplementedError("ReplayBufferRewardWrapper over an image space is not implemented: the relabel "
+                                      "kernels read float32 rows, an image ring holds uint8 frames")
+        self.frames = False
         # (dict observations: the inner buffer refuses anything but a flat Box)
         self.replay_buffer = replay_buffer_class(buffer_size, observation_space, action_space, **kwargs)
         self.reward_fn = reward_fn

@@ -54,10 +54,13 @@ class SQILReplayBuffer(dqn.ReplayBuffer):
         if not isinstance(demonstrations, dt.Transitions):
             raise NotImplementedError(f"Unsupported demonstrations type: {demonstrations}")
         n = len(demonstrations)
+        if self.frames and not (np.asarray(demonstrations.obs).dtype == np.uint8
+                                and np.asarray(demonstrations.next_obs).dtype == np.uint8):
+            raise ValueError("demonstrations for an image space must hold uint8 frames (they are stored as they come)")
         # one `add` per demonstration into a ring of n positions with one env each: reward 1, the table is full afterwards
         self.expert_index = dqn.ReplayIndex(n, 1)
         self.expert_index.fill()
-        self.expert = dqn._Table(n, self.obs_dim, self.device, self.act_dim)
+        self.expert = dqn._Table(n, self.obs_dim, self.device, self.act_dim, frames=self.frames)
         self.expert.write(0, demonstrations.obs, demonstrations.next_obs, demonstrations.acts, np.ones(n, np.float32),
                           demonstrations.dones)
 

@@ -937,6 +937,19 @@ int ia_dqn_adam_step(float* params, const float* grads, float* exp_avg, float* e
                      double beta2, float eps, float weight_decay, float step_size, float bc2_sqrt, void* stream);
 /* [SB3 utils.polyak_update] target = tau * online + (1 - tau) * target over n floats (tau == 1: a copy). */
 int ia_polyak_update(const float* online, float* target, int64_t n, float tau, void* stream);
+/* DQN on image observations (csrc/dqn_frames.hip): the minibatch of index row idx[B] from the two uint8 frame tables in
+ * ONE launch (rows < n_new index the learner ring, the rest the expert table, as in ia_dqn_update; a table no row comes
+ * from may be NULL). Per table: obs / next_obs uint8 [rows, frame_bytes], action int64 [rows], reward, done float [rows].
+ * Outputs, contiguous: obs_out / next_out uint8 [B, frame_bytes], act_out int64 [B], rew_out / done_out float [B]. Pure
+ * data movement, bit-exact: 16-byte words where a row's source, its destination and the chunk allow it, else 4-byte words
+ * or bytes, the tail byte by byte (rows are only frame_bytes-aligned). The caller validates idx against the row counts;
+ * an index outside [0, rows) writes nothing. IA_ERR_ARG for B <= 0, n_new outside [0, B], frame_bytes < 1, a NULL output
+ * or a NULL table that rows are drawn from; IA_ERR_UNSUPPORTED for frame_bytes above 65535 * 4096. */
+int ia_dqn_assemble_u8(const uint8_t* ring_obs, const uint8_t* ring_next_obs, const int64_t* ring_act, const float* ring_rew,
+                       const float* ring_done, int64_t ring_rows, const uint8_t* exp_obs, const uint8_t* exp_next_obs,
+                       const int64_t* exp_act, const float* exp_rew, const float* exp_done, int64_t exp_rows,
+                       const int64_t* idx, int B, int n_new, int64_t frame_bytes, uint8_t* obs_out, uint8_t* next_out,
+                       int64_t* act_out, float* rew_out, float* done_out, void* stream);
 
 /* ---- TD3 / DDPG ([SB3 td3/td3.py] TD3.train; csrc/td3.hip) -------------------------------------------------------
  * The pieces of one gradient step around ia_mlp_forward / ia_mlp_backward (actor D -> ... -> A with a tanh output,
