@@ -6599,8 +6599,9 @@ int ia_ppo_minibatch(const ia_policy_desc* d, float* params, float* params_t, fl
 }
 
 // Data-parallel split of a minibatch step (one rank per GPU): `_grad` = statistics + forward/backward
-// + fixed-order slab reduction into the flat gradient at ia_ppo_grad_ptr(); the caller all-reduces
-// that buffer over RCCL; `_apply` = clip_grad_norm_ + Adam on the reduced gradient.
+// + fixed-order slab reduction into the flat gradient at ws + ia_ppo_grad_offset() floats (unclipped, the mean-loss
+// gradient of the local rows); the caller all-reduces that buffer over RCCL; `_apply` = clip_grad_norm_ + Adam on the
+// reduced gradient.
 int ia_ppo_minibatch_grad(const ia_policy_desc* d, float* params, float* params_t, float* norm_mean, float* norm_var,
                           int32_t* norm_count, int update_norm, const float* obs, const float* actions,
                           const float* old_logp, const float* advantages, const float* returns, const int64_t* idx,

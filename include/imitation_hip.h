@@ -561,6 +561,10 @@ int ia_ppo_minibatch_grad(const ia_policy_desc* d, float* params, float* params_
                           const float* old_logp, const float* advantages, const float* returns, const int64_t* idx,
                           int batch, int T, int n_envs, int normalize_adv, float clip_range, float ent_coef,
                           float vf_coef, float* ws, void* stream);
+/* Float offset into ws of the flat gradient `_grad` leaves (ia_policy_param_count floats, the parameters' order): the
+ * UNCLIPPED gradient of the mean loss pg + ent_coef * entropy + vf_coef * value over the `batch` local rows -- no
+ * clip_grad_norm_, no Adam, parameters and moments untouched. `_apply` reads it there and leaves it as it found it
+ * (tests/test_ppo_gradient_gpu.py pins both against float64). */
 int64_t ia_ppo_grad_offset(const ia_policy_desc* d, int batch);
 /* Debug/measurement: when set to a device buffer of 32 int64, block 0 of every ppo_grad launch
  * stores the shader clock at its phase boundaries in [0..11]; ia_ppo_update accumulates 100 MHz ticks

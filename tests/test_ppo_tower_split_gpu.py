@@ -20,10 +20,11 @@ def _need_gpu():
     L.load()
 
 
-def _inputs(D, A, discrete, norm, T, n):
-    """Seeded policy and rollout, built as `test_ppo_epochs_match_oracle` builds them (no oracle run)."""
-    pol = _oracle_policy(D, A, 32, discrete, norm, seed=3)
-    rng = np.random.default_rng(0)
+def _host_inputs(D, A, discrete, norm, T, n, H=32, seed=0):
+    """Seeded policy and rollout on the host, built as `test_ppo_epochs_match_oracle` builds them (no oracle run, no
+    device): time-major arrays and the two permutations `np.random.seed(123)` gives `RolloutBuffer.get`."""
+    pol = _oracle_policy(D, A, H, discrete, norm, seed=3)
+    rng = np.random.default_rng(seed)
     aw = 1 if discrete else A
     obs = rng.standard_normal((T, n, D)).astype(np.float32)
     act = (rng.integers(0, A, (T, n, 1)) if discrete else rng.standard_normal((T, n, A))).astype(np.float32)
@@ -38,10 +39,22 @@ def _inputs(D, A, discrete, norm, T, n):
     logp = (lp.numpy() + 0.1 * rng.standard_normal(T * n)).reshape(T, n).astype(np.float32)
     np.random.seed(123)
     perms = np.stack([np.random.permutation(T * n) for _ in range(2)])
+    return pol, dict(obs=obs, act=act, lp=logp, adv=adv, ret=ret, perm=perms)
+
+
+def _upload(host):
+    """The host rollout of `_host_inputs` on the device."""
+    obs, act, logp, adv, ret, perms = (host[k] for k in ("obs", "act", "lp", "adv", "ret", "perm"))
+    T = obs.shape[0]
     # (one time slice more than T behind the observations, as the rollout tile has: rows are read in 16-byte pieces)
     d_obs = dev(np.concatenate([obs, np.zeros_like(obs[:1])]))[:T]
-    return pol, dict(obs=d_obs, act=dev(act), lp=dev(logp), adv=dev(adv), ret=dev(ret),
-                     perm=th.as_tensor(perms).to(DEV))
+    return dict(obs=d_obs, act=dev(act), lp=dev(logp), adv=dev(adv), ret=dev(ret), perm=th.as_tensor(perms).to(DEV))
+
+
+def _inputs(D, A, discrete, norm, T, n, H=32, seed=0):
+    """`_host_inputs` with the rollout on the device."""
+    pol, host = _host_inputs(D, A, discrete, norm, T, n, H, seed)
+    return pol, _upload(host)
 
 
 def _run(pol, rows, D, A, discrete, norm, T, n, bs, split, launches):
