@@ -107,6 +107,16 @@ class OffpolicyStepArgs(C.Structure):
                 [("tile_row", C.c_int64), ("tile_rows", C.c_int64), ("rewards_host", C.c_void_p)])
 
 
+class OffpolicyFramesArgs(C.Structure):
+    """Mirror of `ia_offpolicy_frames_args` (include/imitation_hip.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("obs", "next_obs", "act", "dones", "ring_done")] +
+                [(n, C.c_int) for n in ("n", "C", "H", "W", "use_state", "use_next_state")] +
+                [(n, C.c_void_p) for n in ("lut", "X", "ring_obs", "ring_next_obs", "ring_action", "ring_reward",
+                                           "ring_done_out")] + [("ring_row", C.c_int64), ("ring_rows", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("tile_obs", "tile_next_obs", "tile_act", "tile_dones")] +
+                [("tile_row", C.c_int64), ("tile_rows", C.c_int64), ("rewards_host", C.c_void_p)])
+
+
 class ReplayRelabelArgs(C.Structure):
     """Mirror of `ia_replay_relabel_args` (include/imitation_hip.h)."""
     _fields_ = ([(n, C.c_void_p) for n in ("obs", "next_obs", "act_f32", "act_i64", "done")] + [("ring_rows", C.c_int64)] +
@@ -331,6 +341,11 @@ _SIGS = {
     "ia_offpolicy_step_rows": ([], C.c_int),
     "ia_offpolicy_step_ok": ([C.POINTER(MlpDesc), _I, _I, _I, _I, _I, _I], C.c_int),
     "ia_offpolicy_step": ([C.POINTER(OffpolicyStepArgs), _P], C.c_int),
+    "ia_offpolicy_frames_step": ([C.POINTER(OffpolicyFramesArgs), _P], C.c_int),
+    "ia_offpolicy_frames_reward": ([C.POINTER(OffpolicyFramesArgs), _P, _I, _P, _I, _I, _I, _I, _P], C.c_int),
+    "ia_disc_gather_frames": ([_P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+                              C.c_int),
+    "ia_gather_frame_rows": ([_P, _P, _P, _P, _L, _P, _L, _L, _P, _P, _P, _P, _L, _L, _P], C.c_int),
     "ia_replay_relabel_ok": ([C.POINTER(MlpDesc), _I, _I, _I, _I, _I, _I], C.c_int),
     "ia_replay_relabel": ([C.POINTER(ReplayRelabelArgs), _P], C.c_int),
     "ia_replay_relabel_general_ws_doubles": ([C.POINTER(MlpDesc), _L], C.c_int64),

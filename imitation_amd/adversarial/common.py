@@ -64,13 +64,21 @@ def _stats_dict(loss, n_correct, n_correct_exp, n_correct_gen, n_pred_gen, ent_s
     }
 
 
-def _upload_table(samples: Mapping, obs_shape, discrete: bool, device) -> TransitionTable:
-    """Explicit `expert_samples` / `gen_samples` dicts (`common.py:317-337,564-583`) -> device rows."""
+def _upload_table(samples: Mapping, obs_shape, discrete: bool, device, frames: bool = False) -> TransitionTable:
+    """Explicit `expert_samples` / `gen_samples` dicts (`common.py:317-337,564-583`) -> device rows. `frames`: the
+    observations are uint8 frames and stay uint8 (the frame path's tables)."""
     def arr(k):
         v = samples[k]
         return v.detach().cpu().numpy() if isinstance(v, th.Tensor) else np.asarray(v)
     n = len(arr("obs"))
     f32 = lambda a: th.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).reshape(n, -1).to(device)
+    if frames:
+        if arr("obs").dtype != np.uint8 or arr("next_obs").dtype != np.uint8 or not discrete:
+            raise ValueError("a frame table stores uint8 frames as they come: the observations must be uint8 arrays")
+        u8 = lambda a: th.from_numpy(np.ascontiguousarray(a)).reshape(n, -1).to(device)
+        return TransitionTable(u8(arr("obs")), th.from_numpy(np.ascontiguousarray(arr("acts"), dtype=np.int64)
+                                                               ).reshape(n).to(device), u8(arr("next_obs")),
+                               th.from_numpy(np.ascontiguousarray(arr("dones"), dtype=np.uint8)).to(device), True)
     acts = arr("acts")
     acts_d = (th.from_numpy(np.ascontiguousarray(acts, dtype=np.int64)).reshape(n).to(device) if discrete
               else f32(acts))
@@ -102,11 +110,25 @@ class AdversarialTrainer(abc.ABC):
         self.allow_variable_horizon = allow_variable_horizon
         self._horizon = None
         self.venv = venv
-        if isinstance(gen_algo, dqn.DQN) and getattr(gen_algo.policy, "frames", False):
-            raise NotImplementedError("adversarial training over a DQN generator with a CnnPolicy is not implemented: the "
-                                      "relabel-and-store step (ia_offpolicy_step) reads float32 rows, the learner's ring "
-                                      "holds uint8 frames")
+        # a DQN generator with a CnnPolicy (uint8 frame ring): GAIL on the frame path (csrc/offpolicy_frames.hip, DESIGN
+        # section 4.18) or, with `IA_OFFPOLICY_FUSED=0` / a reward net that path does not cover, on the generic host path
+        self._frames = isinstance(gen_algo, dqn.DQN) and bool(getattr(gen_algo.policy, "frames", False))
+        if self._needs_logp and self._frames:   # (AIRL over any other DQN: refused the same way, behind the constructor)
+            raise TypeError("AIRL needs a stochastic policy to compute the discriminator output.")
+        if self._frames:
+            if data_parallel is not None:
+                raise NotImplementedError("data_parallel is not implemented for a DQN generator with a CnnPolicy: the "
+                                          "frame ring and the frame tables live on one device")
+            if self.disc_grad_penalty_coef > 0.0:
+                raise NotImplementedError("disc_grad_penalty_coef > 0 is not implemented for a DQN generator with a "
+                                          "CnnPolicy: the penalty interpolates float32 rows, the frame tables hold uint8")
+            if th.device(gen_algo.device).type != "cuda":
+                raise NotImplementedError("adversarial training over a DQN generator with a CnnPolicy has no host "
+                                          "implementation: its frame path (uint8 ring, round tile and discriminator tables, "
+                                          "csrc/offpolicy_frames.hip) runs on the GPU only -- move the generator to 'cuda'")
         self.gen_algo = gen_algo
+        self._frame_path = False   # (decided below, before the demonstrations are uploaded)
+        self.frame_gather_launches = 0   # `ia_disc_gather_frames` calls so far (tests count them)
         # the replay ring's index rows of a round's discriminator updates are drawn by the PPO permutation helper's C call,
         # behind the epoch permutations, on a copy of NumPy's global generator (`_replay_rows_spec`, `_disc_round`)
         self.predraw_disc_indices = True
@@ -151,6 +173,8 @@ class AdversarialTrainer(abc.ABC):
         self._expert_table: Optional[TransitionTable] = None
         self._expert_stream: Optional[dt.ExpertIndexStream] = None
         self._expert_batches = None
+        self.debug_use_ground_truth = debug_use_ground_truth
+        self._frame_path = self._frame_path_ok()
         self.set_demonstrations(demonstrations)
 
         self._global_step = 0
@@ -207,14 +231,17 @@ class AdversarialTrainer(abc.ABC):
             self.gen_train_timesteps = gen_train_timesteps
         if gen_replay_buffer_capacity is None:
             gen_replay_buffer_capacity = self.gen_train_timesteps
-        self._gen_replay_buffer = buffer.ReplayBuffer(gen_replay_buffer_capacity, self.venv, device=self._device)
+        ring_cls = buffer.FrameReplayBuffer if self._frame_path else buffer.ReplayBuffer
+        self._gen_replay_buffer = ring_cls(gen_replay_buffer_capacity, self.venv, device=self._device)
         # off-policy generators (DQN, TD3, DDPG) under a state-holder reward net: one `ia_offpolicy_step` launch per
         # environment step relabels the step and stores it to the learner's ring and to a per-round device tile
         # (`dqn.RewardStepSource`); every other combination keeps the per-step host path of the wrapper
         self._step_source = None
-        if self._offpolicy_fused_ok():
-            self._step_source = dqn.RewardStepSource(self.gen_algo.replay_buffer, self.reward_train,
-                                                       tile_steps=self._round_steps_bound())
+        if self._frame_path or self._offpolicy_fused_ok():
+            # (the frame path: the same step for a uint8 frame ring under a CnnRewardNet, `dqn.FrameRewardStepSource`)
+            source_cls = dqn.FrameRewardStepSource if self._frame_path else dqn.RewardStepSource
+            self._step_source = source_cls(self.gen_algo.replay_buffer, self.reward_train,
+                                           tile_steps=self._round_steps_bound())
             self.gen_algo.replay_buffer.reward_source = self._step_source
             self.venv_wrapped.step_source = self._step_source
 
@@ -338,7 +365,8 @@ class AdversarialTrainer(abc.ABC):
         self._bce_ws = th.zeros(int(L.load().ia_bce_ws_floats(2 * self.demo_minibatch_size)), device=self._device)
         self._dlogits = th.zeros(2 * self.demo_minibatch_size, device=self._device)
         self._logp = th.zeros(2 * self.demo_minibatch_size, device=self._device)
-        od = int(np.prod(venv.observation_space.shape))
+        # (the policy-pass rows: only actor-critic policies have that pass, a frame generator's rows are never assembled)
+        od = 1 if self._frames else int(np.prod(venv.observation_space.shape))
         ad = 1 if self._discrete else int(np.prod(venv.action_space.shape))
         self._pol_obs = th.zeros(2 * self.demo_minibatch_size, od, device=self._device)
         self._pol_act = th.zeros(2 * self.demo_minibatch_size, max(ad, 1), device=self._device)
@@ -388,7 +416,8 @@ class AdversarialTrainer(abc.ABC):
         self._expert_batches = None
         self._expert_stream = dt.ExpertIndexStream(len(demos), self.demo_batch_size)
         self._expert_table = _upload_table(dict(obs=demos.obs, acts=demos.acts, next_obs=demos.next_obs,
-                                                dones=demos.dones), None, self._discrete, self._device)
+                                                dones=demos.dones), None, self._discrete, self._device,
+                                           frames=self._frame_path)
 
     def _check_fixed_horizon(self, horizons: Iterable[int]) -> None:
         """`algorithms/base.py:77-110`."""
@@ -453,10 +482,11 @@ class AdversarialTrainer(abc.ABC):
             else:
                 self._ring_rows_drawn.append(k)
         obs_shape = self.venv.observation_space.shape
+        fr = self._frame_path
         e_tab = self._expert_table if expert_samples is None else _upload_table(expert_samples, obs_shape,
-                                                                                self._discrete, self._device)
+                                                                                self._discrete, self._device, frames=fr)
         g_tab = self._gen_replay_buffer.table if gen_samples is None else _upload_table(gen_samples, obs_shape,
-                                                                                        self._discrete, self._device)
+                                                                                        self._discrete, self._device, frames=fr)
         return (e_tab, e_idx), (g_tab, g_idx)
 
     def _upload_index_rows(self) -> None:
@@ -738,7 +768,8 @@ class AdversarialTrainer(abc.ABC):
         (e_tab, e_idx), (g_tab, g_idx) = drawn if drawn is not None else self._batch_sources(expert_samples,
                                                                                                gen_samples)
         if self._module_net:
-            self._disc_update_module((e_tab, e_idx), (g_tab, g_idx), stats_dev, quirk_done)
+            update = self._disc_update_frames if self._frame_path else self._disc_update_module
+            update((e_tab, e_idx), (g_tab, g_idx), stats_dev, quirk_done)
             return
         B, mb = self.demo_batch_size, self.demo_minibatch_size
         scale = mb / B
@@ -1047,6 +1078,59 @@ class AdversarialTrainer(abc.ABC):
         stats_dev.copy_(stats)
         self._disc_step += 1
         self._last_disc_logits = logits.detach()
+
+    def _disc_update_frames(self, e_src, g_src, stats_dev: th.Tensor, quirk_done: bool) -> None:
+        """`_disc_update_module` on the frame path: both tables hold uint8 frames. Per minibatch ONE
+        `ia_disc_gather_frames` launch builds the CNN's channel-last fp32 input, the int64 actions and the fp32 dones of
+        [expert rows | generator rows]; then `forward_nhwc`, the BCE, `backward()`; the optimiser step behind the last.
+        (A DQN policy has no policy pass; statistics, counters and draw order are `_disc_update_module`'s.)"""
+        from imitation_amd import ops
+        (e_tab, e_idx), (g_tab, g_idx) = e_src, g_src
+        B, mb = self.demo_batch_size, self.demo_minibatch_size
+        net = self._reward_net
+        C_, H, W = self.venv.observation_space.shape
+        n_act = int(self.venv.action_space.n)
+        S = int(net.use_state) + int(net.use_next_state)
+        lut = ops._byte_lut(self._device)
+        for tab in (e_tab, g_tab):
+            if tab.obs.dtype != th.uint8 or tab.next_obs.dtype != th.uint8 or not tab.discrete:
+                raise TypeError("the frame path's discriminator update reads uint8 frame tables with Discrete actions")
+        self._disc_opt.zero_grad()
+        stats = logits = None
+        for start in range(0, B, mb):
+            # (explicit samples come without index rows: rows start .. start + mb - 1 of their table)
+            rows = [idx[start:start + mb] if idx is not None else th.arange(start, start + mb, device=self._device)
+                    for idx in (e_idx, g_idx)]
+            X = th.empty(2 * mb, H, W, C_ * S, device=self._device)
+            acts = th.empty(2 * mb, dtype=th.int64, device=self._device)
+            dones = th.empty(2 * mb, device=self._device)
+            L.call("ia_disc_gather_frames", L.ptr(e_tab.obs), L.ptr(e_tab.next_obs), L.ptr(e_tab.acts), L.ptr(e_tab.dones),
+                   len(e_tab), L.ptr(g_tab.obs), L.ptr(g_tab.next_obs), L.ptr(g_tab.acts), L.ptr(g_tab.dones), len(g_tab),
+                   L.ptr(rows[0].contiguous()), L.ptr(rows[1].contiguous()), mb, H, W, C_, int(net.use_state),
+                   int(net.use_next_state), L.ptr(lut), L.ptr(X), L.ptr(acts), L.ptr(dones), L.stream())
+            self.frame_gather_launches += 1
+            onehot = th.nn.functional.one_hot(acts, num_classes=n_act).float()
+            logits = net.forward_nhwc(X, onehot, dones)
+            loss, stats = ops.bce_expert_first(logits, mb, mb / B)
+            loss.backward()
+        self._disc_opt.step()
+        stats_dev.copy_(stats)
+        self._disc_step += 1
+        self._last_disc_logits = logits.detach()
+
+    def _frame_path_ok(self) -> bool:
+        """A DQN generator with a CnnPolicy on the GPU whose ring is exactly `dqn.ReplayBuffer`, GAIL over a reward net the
+        frame path's reward launch covers (`dqn.frame_reward_plan`: `modules.CnnRewardNet`, channel-first, images
+        normalised), and `IA_OFFPOLICY_FUSED` is not 0. Everything else over an image space takes the generic host path."""
+        if not self._frames or self._needs_logp or self.debug_use_ground_truth:
+            return False
+        from imitation_amd.adversarial import gail   # (imports this module: resolved by the time a trainer is built)
+        ring = getattr(self.gen_algo, "replay_buffer", None)
+        return (type(ring) is dqn.ReplayBuffer and ring.frames and self._discrete
+                and dqn.frame_reward_plan(self.reward_train) is not None
+                # (`_disc_update_frames` forms GAIL's logits itself: a subclass with logits of its own keeps the host path)
+                and type(self).logits_expert_is_high is gail.GAIL.logits_expert_is_high
+                and os.environ.get("IA_OFFPOLICY_FUSED", "1") != "0")
 
     def _module_grad_penalty(self, state, action, next_state, done, mb: int, scale: float) -> None:
         from imitation_amd import grad_penalty, modules

@@ -189,3 +189,81 @@ class ReplayBuffer:
             "next_obs": self._next.cpu().numpy().reshape(c, *self.obs_shape).astype(self.obs_dtype),
             "dones": self._dones.cpu().numpy().astype(bool),
         }
+
+
+class FrameReplayBuffer(ReplayBuffer):
+    """`ReplayBuffer` over a uint8 image space as a uint8 table: `obs` / `next_obs` uint8 `[capacity, C*H*W]`, the frames
+    as the environment hands them over (a quarter of the float32 ring's bytes), discrete actions int64, dones uint8. The
+    same draws from NumPy's global generator and the same index arithmetic as `ReplayBuffer`; `store_from_rollout` moves
+    the round tile of `dqn.FrameRewardStepSource` into the ring with one `ia_gather_frame_rows` launch
+    (csrc/offpolicy_frames.hip), which wraps at the capacity itself."""
+
+    def __init__(self, capacity: int, venv=None, *, obs_shape=None, act_shape=None, obs_dtype=None, act_dtype=None,
+                 device="cuda"):
+        if venv is not None:
+            if obs_shape is not None or act_shape is not None or obs_dtype is not None or act_dtype is not None:
+                raise ValueError("Cannot specify both shapes/dtypes and also an environment.")
+            obs_shape, obs_dtype = tuple(venv.observation_space.shape), venv.observation_space.dtype
+            act_shape, act_dtype = tuple(venv.action_space.shape), venv.action_space.dtype
+            self.discrete = isinstance(venv.action_space, spaces.Discrete)
+        else:
+            if any(x is None for x in (obs_shape, act_shape, obs_dtype, act_dtype)):
+                raise ValueError("Shape or dtype missing and no environment specified.")
+            self.discrete = len(tuple(act_shape)) == 0 and np.issubdtype(np.dtype(act_dtype), np.integer)
+        if np.dtype(obs_dtype) != np.uint8 or not self.discrete:
+            raise TypeError("FrameReplayBuffer holds uint8 frames and Discrete actions")
+        self.capacity = int(capacity)
+        self.obs_shape, self.act_shape = tuple(obs_shape), tuple(act_shape)
+        self.obs_dtype, self.act_dtype = np.dtype(obs_dtype), np.dtype(act_dtype)
+        self.device = th.device(device)
+        od = int(np.prod(self.obs_shape))
+        self._obs = th.zeros(self.capacity, od, dtype=th.uint8, device=self.device)
+        self._next = th.zeros(self.capacity, od, dtype=th.uint8, device=self.device)
+        self._acts = th.zeros(self.capacity, dtype=th.int64, device=self.device)
+        self._dones = th.zeros(self.capacity, dtype=th.uint8, device=self.device)
+        self._infos: Optional[np.ndarray] = None
+        self._n_data = 0
+        self._idx = 0
+        self.table = TransitionTable(self._obs, self._acts, self._next, self._dones, True)
+
+    def _put(self, lo: int, obs, acts, nxt, dones) -> None:
+        hi = lo + len(obs)
+        obs, nxt = np.asarray(obs), np.asarray(nxt)
+        if obs.dtype != np.uint8 or nxt.dtype != np.uint8:
+            raise ValueError("a frame table stores uint8 frames as they come: the observations must be uint8 arrays")
+        self._obs[lo:hi].copy_(th.from_numpy(np.ascontiguousarray(obs)).reshape(len(obs), -1))
+        self._next[lo:hi].copy_(th.from_numpy(np.ascontiguousarray(nxt)).reshape(len(obs), -1))
+        self._acts[lo:hi].copy_(th.from_numpy(np.ascontiguousarray(acts, dtype=np.int64)).reshape(-1))
+        self._dones[lo:hi].copy_(th.from_numpy(np.ascontiguousarray(dones, dtype=np.uint8)))
+
+    def store_from_rollout(self, rb, order: np.ndarray, truncate_ok: bool = True, infos=None) -> None:
+        """`store` for transitions in a uint8 round tile `rb` (`dqn.FrameRewardStepSource.rollout_view`): rows `order`
+        gathered device-to-device into the ring; same index arithmetic as `ReplayBuffer.store_from_rollout`."""
+        from imitation_amd import _lib as L
+        n = len(order)
+        if n == 0:
+            raise ValueError("Trying to store empty data.")
+        if n > self.capacity:
+            if not truncate_ok:
+                raise ValueError("Not enough capacity to store data.")
+            order = order[-self.capacity:]
+            infos = None if infos is None else infos[-self.capacity:]
+            n = self.capacity
+        infos = self._meaningful(infos)
+        order = np.ascontiguousarray(order, dtype=np.int64)
+        src_rows = rb.buffer_size * rb.n_envs
+        if int(order.min()) < 0 or int(order.max()) >= src_rows:
+            raise IndexError(f"a row of the order lies outside the round tile ({src_rows} rows)")
+        order_dev = th.from_numpy(order).to(self.device)
+        od = self._obs.shape[1]
+        L.call("ia_gather_frame_rows", L.ptr(rb.obs), L.ptr(rb.next_fixed), L.ptr(rb.clipped), L.ptr(rb.dones), src_rows,
+               L.ptr(order_dev), n, od, L.ptr(self._obs), L.ptr(self._next), L.ptr(self._acts), L.ptr(self._dones),
+               self._idx, self.capacity, L.stream())
+        if self._idx + n > self.capacity:
+            rem = self.capacity - self._idx
+            self._put_infos(self._idx, None if infos is None else infos[:rem], rem)
+            self._put_infos(0, None if infos is None else infos[rem:], n - rem)
+        else:
+            self._put_infos(self._idx, infos, n)
+        self._idx = (self._idx + n) % self.capacity
+        self._n_data = min(self._n_data + n, self.capacity)

@@ -396,6 +396,177 @@ class _RoundTile(NamedTuple):
     n_envs: int
 
 
+def frame_reward_plan(reward_net):
+    """(cnn_net, softplus) when `reward_net` is what the frame path's reward launch covers -- `modules.CnnRewardNet` over
+    channel-first frames with `normalize_images`, plain or under GAIL's `RewardNetFromDiscriminatorLogit` --, else None."""
+    from imitation_amd import modules
+    net, softplus = reward_net, False
+    if type(net) is modules.RewardNetFromDiscriminatorLogit:
+        net, softplus = net.base, True
+    if type(net) is not modules.CnnRewardNet or net.hwc_format or not net.normalize_images:
+        return None
+    return net, softplus
+
+
+class FrameRewardStepSource:
+    """`RewardStepSource` for a uint8 frame ring under a `modules.CnnRewardNet` (csrc/offpolicy_frames.hip): per environment
+    step ONE `ia_offpolicy_frames_step` launch reads the step's frames once from a pinned host record and writes them to the
+    learner's ring, to the uint8 round tile and, as channel-last fp32 through the byte table, to the reward CNN's input;
+    the CNN runs under `no_grad` (`forward_nhwc`, the convolution ops); ONE `ia_offpolicy_frames_reward` launch selects
+    the action's (and done's) output, applies GAIL's softplus and writes the rewards to the ring and to the pinned host
+    reward tile. Same surface, same ring of pinned records with one event per record as `RewardStepSource`."""
+
+    SLOTS = 8
+
+    def __init__(self, ring: "ReplayBuffer", reward_net, slots: Optional[int] = None, tile_steps: int = 64):
+        from imitation_amd import ops
+        if not ring.frames or ring.act_dim is not None:
+            raise TypeError("FrameRewardStepSource stores uint8 frames with Discrete actions (RewardStepSource stores "
+                            "float32 rows)")
+        require_device(ring.device)
+        plan = frame_reward_plan(reward_net)
+        if plan is None:
+            raise NotImplementedError("the frame path's reward launch covers modules.CnnRewardNet(hwc_format=False) with "
+                                      "normalize_images, plain or under GAIL's softplus; any other net takes the host path")
+        self.ring, self.net = ring, reward_net
+        self.cnn_net, self.softplus = plan
+        self.device = ring.device
+        self.n, self.od = ring.n_envs, ring.obs_dim
+        self.shape = tuple(ring.observation_space.shape)          # (C, H, W)
+        self.n_actions = int(ring.action_space.n)
+        c = self.cnn_net
+        self.S = int(c.use_state) + int(c.use_next_state)
+        self.n_out = (self.n_actions if c.use_action else 1) * (2 if c.use_done else 1)
+        self.lut = ops._byte_lut(self.device)
+        C_, H, W = self.shape
+        self.X = th.empty(self.n, H, W, C_ * self.S, device=self.device)
+        n, od = self.n, self.od
+        pin = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype).pin_memory()
+        self.slots = []
+        for _ in range(int(slots or self.SLOTS)):
+            rec = dict(obs=pin(n, od, dtype=th.uint8), next_obs=pin(n, od, dtype=th.uint8), dones=pin(n, dtype=th.uint8),
+                       ring_done=pin(n), act=pin(n, dtype=th.int64))
+            rec["np"] = {k: v.numpy() for k, v in rec.items()}
+            self.slots.append(rec)
+        self.events: List[Optional[th.cuda.Event]] = [None] * len(self.slots)
+        self.launches = 0          # `ia_offpolicy_frames_step` calls so far (tests count them)
+        self.reward_launches = 0   # `ia_offpolicy_frames_reward` calls so far
+        self._slot_checked = -1
+        self._staged = -1
+        self.event_waits = 0
+        self.tile_step = 0
+        self._alloc_tile(int(tile_steps))
+        self._args: List[Any] = [None] * len(self.slots)
+
+    def _alloc_tile(self, steps: int) -> None:
+        n, od, dev = self.n, self.od, self.device
+        old = getattr(self, "tile_obs", None)
+        olds = (self.tile_obs, self.tile_next, self.tile_act, self.tile_dones, self.rewards_host) if old is not None else None
+        self.tile_cap = steps
+        self.tile_obs = th.zeros(steps * n, od, dtype=th.uint8, device=dev)
+        self.tile_next = th.zeros(steps * n, od, dtype=th.uint8, device=dev)
+        self.tile_act = th.zeros(steps * n, dtype=th.int64, device=dev)
+        self.tile_dones = th.zeros(steps * n, dtype=th.uint8, device=dev)
+        self.rewards_host = th.zeros(steps, n).pin_memory()
+        self.rewards_np = self.rewards_host.numpy()
+        if olds is not None:   # a longer round than any before: the written rows move over (rare; one synchronisation)
+            th.cuda.current_stream().synchronize()
+            for new, o in zip((self.tile_obs, self.tile_next, self.tile_act, self.tile_dones, self.rewards_host), olds):
+                m = min(len(o), len(new))
+                new[:m].copy_(o[:m])
+            th.cuda.current_stream().synchronize()
+
+    def reward_row(self) -> np.ndarray:
+        """The row of the pinned reward tile the NEXT stored step fills (valid once its reward launch has completed)."""
+        if self.tile_step == self.tile_cap:
+            self._alloc_tile(2 * self.tile_cap)
+        return self.rewards_np[self.tile_step]
+
+    def _slot(self):
+        k = self.launches % len(self.slots)
+        if self._slot_checked != self.launches:   # (once per step: `stage` and `store_step` fill the same record)
+            self._slot_checked = self.launches
+            ev = self.events[k]
+            if ev is not None and not ev.query():
+                self.event_waits += 1
+                ev.synchronize()
+        return k, self.slots[k]["np"]
+
+    def stage(self, actions, dones) -> None:
+        """The action the environment executed and the raw dones of the step."""
+        _, rec = self._slot()
+        rec["act"][...] = np.asarray(actions).reshape(rec["act"].shape)
+        rec["dones"][...] = np.asarray(dones).reshape(-1)
+        self._staged = self.launches
+
+    def require_staged(self) -> None:
+        if self._staged != self.launches:
+            raise RuntimeError("ReplayBuffer.add on a ring with a reward source needs the step staged by the "
+                               "RewardVecEnvWrapper the trainer built (stage() was not called for this step)")
+
+    def store_step(self, ring_row: int, obs, next_obs, ring_action, ring_done) -> None:
+        self.require_staged()
+        k, rec = self._slot()
+        n = self.n
+        obs, next_obs = np.asarray(obs), np.asarray(next_obs)
+        if obs.dtype != np.uint8 or next_obs.dtype != np.uint8:
+            raise ValueError("a frame table stores uint8 frames as they come: the observations must be uint8 arrays")
+        rec["obs"][...] = obs.reshape(n, -1)
+        rec["next_obs"][...] = next_obs.reshape(n, -1)
+        rec["ring_done"][...] = ring_done
+        if self.tile_step == self.tile_cap:
+            self._alloc_tile(2 * self.tile_cap)
+        a = self._slot_args(k)
+        a.ring_row, a.tile_row = int(ring_row), self.tile_step * n
+        a.rewards_host = self.rewards_host.data_ptr() + 4 * self.tile_step * n
+        lib, st = L.load(), L.stream()
+        L.check(lib.ia_offpolicy_frames_step(C.byref(a), st), "ia_offpolicy_frames_step")
+        with th.no_grad():
+            out = self.cnn_net.cnn.forward_nhwc(self.X).contiguous()
+        c = self.cnn_net
+        L.check(lib.ia_offpolicy_frames_reward(C.byref(a), out.data_ptr(), self.n_out, None, self.n_actions,
+                                               int(c.use_action), int(c.use_done), int(self.softplus), st),
+                "ia_offpolicy_frames_reward")
+        if self.events[k] is None:
+            self.events[k] = th.cuda.Event()
+        self.events[k].record()
+        self.last_event = self.events[k]
+        self.launches += 1
+        self.reward_launches += 1
+        self.tile_step += 1
+
+    def _slot_args(self, k: int):
+        """The argument record of pinned record `k`; refilled when the round tile has moved."""
+        key = self.tile_obs.data_ptr()
+        if self._args[k] is not None and self._args[k][0] == key:
+            return self._args[k][1]
+        slot, t, a = self.slots[k], self.ring.table, L.OffpolicyFramesArgs()
+        a.obs, a.next_obs, a.act = slot["obs"].data_ptr(), slot["next_obs"].data_ptr(), slot["act"].data_ptr()
+        a.dones, a.ring_done = slot["dones"].data_ptr(), slot["ring_done"].data_ptr()
+        a.n, (a.C, a.H, a.W) = self.n, self.shape
+        a.use_state, a.use_next_state = int(self.cnn_net.use_state), int(self.cnn_net.use_next_state)
+        a.lut, a.X = self.lut.data_ptr(), self.X.data_ptr()
+        a.ring_obs, a.ring_next_obs, a.ring_action = t.obs.data_ptr(), t.next_obs.data_ptr(), t.action.data_ptr()
+        a.ring_reward, a.ring_done_out, a.ring_rows = t.reward.data_ptr(), t.done.data_ptr(), t.rows
+        a.tile_obs, a.tile_next_obs = self.tile_obs.data_ptr(), self.tile_next.data_ptr()
+        a.tile_act, a.tile_dones, a.tile_rows = self.tile_act.data_ptr(), self.tile_dones.data_ptr(), self.tile_cap * self.n
+        self._args[k] = (key, a)
+        return a
+
+    def wait(self) -> None:
+        """Until the latest reward launch has completed (its rewards are then in the pinned tile)."""
+        if self.launches:
+            self.last_event.synchronize()
+
+    def rollout_view(self):
+        """The round tile with the fields `buffer.FrameReplayBuffer.store_from_rollout` reads."""
+        T, n = self.tile_step, self.n
+        return _RoundTile(self.tile_obs[:T * n], self.tile_next[:T * n], self.tile_act[:T * n], self.tile_dones[:T * n], T, n)
+
+    def reset_tile(self) -> None:
+        self.tile_step = 0
+
+
 class QNetwork:
     """[SB3 dqn.policies.QNetwork]: `create_mlp(features_dim, n_actions, net_arch, activation_fn)` over the flattened
     observation; parameters as one flat device vector in torch's `parameters()` order."""

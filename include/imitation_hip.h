@@ -1052,6 +1052,52 @@ int ia_offpolicy_step_ok(const ia_mlp_desc* d, int obs_dim, int act_dim, int use
                          int use_done);
 int ia_offpolicy_step(const ia_offpolicy_step_args* a, void* stream);
 
+/* ---- the same step on uint8 frames (csrc/offpolicy_frames.hip): GAIL over DQN("CnnPolicy") ------------------------------
+ * Frames are channel-first uint8 rows of C * H * W bytes. `lut` is the 256-entry table byte -> float (byte / 255).
+ * ia_offpolicy_frames_step, ONE launch per environment step: reads the step's n transitions once from a pinned host record
+ * (obs / next_obs uint8 [n, C*H*W], act int64 [n], dones uint8 [n], ring_done float32 [n]) and writes
+ *   rows ring_row .. ring_row + n - 1 of the learner's ring (ring_obs / ring_next_obs uint8, ring_action int64,
+ *     ring_done_out float32; [ring_rows] rows),
+ *   rows tile_row .. tile_row + n - 1 of the round tile (tile_obs / tile_next_obs uint8, tile_act int64, tile_dones uint8;
+ *     [tile_rows] rows),
+ *   X[n, H, W, C * (use_state + use_next_state)] float32, state channels first, every value lut[byte] (X may be NULL).
+ * ring_row + n <= ring_rows and tile_row + n <= tile_rows are checked here (IA_ERR_ARG, nothing is written).
+ * ia_offpolicy_frames_reward, ONE launch behind the reward CNN: from cnn_out [n, n_out] (n_out = (use_action ? n_actions :
+ * 1) * (use_done ? 2 : 1)) the entry CnnRewardNet._select picks with the step's action and raw done (read from the round
+ * tile's rows), softplus(x) = max(x, 0) + log1p(exp(-|x|)) when `softplus`; or, instead, a ready device vector rewards_in
+ * [n] (exactly one of cnn_out / rewards_in). The n rewards go to ring_reward[ring_row ..] and to rewards_host (pinned host
+ * memory, nullable). An action outside [0, n_actions) yields NaN. */
+typedef struct {
+  const uint8_t* obs; const uint8_t* next_obs; const int64_t* act; const uint8_t* dones; const float* ring_done;
+  int n, C, H, W, use_state, use_next_state;
+  const float* lut; float* X;
+  uint8_t* ring_obs; uint8_t* ring_next_obs; int64_t* ring_action; float* ring_reward; float* ring_done_out;
+  int64_t ring_row, ring_rows;
+  uint8_t* tile_obs; uint8_t* tile_next_obs; int64_t* tile_act; uint8_t* tile_dones;
+  int64_t tile_row, tile_rows;
+  float* rewards_host;
+} ia_offpolicy_frames_args;
+int ia_offpolicy_frames_step(const ia_offpolicy_frames_args* a, void* stream);
+int ia_offpolicy_frames_reward(const ia_offpolicy_frames_args* a, const float* cnn_out, int n_out, const float* rewards_in,
+                               int n_actions, int use_action, int use_done, int softplus, void* stream);
+/* One discriminator minibatch from two uint8 transition tables (obs / next_obs uint8 [rows, C*H*W], act int64 [rows], dones
+ * uint8 [rows]): rows idx_e[mb] of the expert table first, then rows idx_g[mb] of the generator ring.
+ * X[2 mb, H, W, C * (use_state + use_next_state)] float32 through lut, state channels first; acts int64 [2 mb]; dones
+ * float32 [2 mb]. A row index outside [0, rows) of its table yields NaN in its X row and touches nothing else. */
+int ia_disc_gather_frames(const uint8_t* e_obs, const uint8_t* e_next_obs, const int64_t* e_act, const uint8_t* e_dones,
+                          int64_t e_rows, const uint8_t* g_obs, const uint8_t* g_next_obs, const int64_t* g_act,
+                          const uint8_t* g_dones, int64_t g_rows, const int64_t* idx_e, const int64_t* idx_g, int mb, int H,
+                          int W, int C, int use_state, int use_next_state, const float* lut, float* X, int64_t* acts,
+                          float* dones, void* stream);
+/* Row (dst_row + i) % dst_rows of the destination ring = source row order[i], for i < n: obs / next_obs uint8 rows of
+ * frame_bytes bytes, act int64, dones uint8, every source array with at least src_rows rows. n <= dst_rows (IA_ERR_ARG
+ * otherwise); an order entry outside [0, src_rows) writes nothing. Device to device, bit-exact; the index arithmetic and
+ * the wrap of buffer.ReplayBuffer.store. */
+int ia_gather_frame_rows(const uint8_t* src_obs, const uint8_t* src_next_obs, const int64_t* src_act,
+                         const uint8_t* src_dones, int64_t src_rows, const int64_t* order, int64_t n, int64_t frame_bytes,
+                         uint8_t* dst_obs, uint8_t* dst_next_obs, int64_t* dst_act, uint8_t* dst_dones, int64_t dst_row,
+                         int64_t dst_rows, void* stream);
+
 /* ---- sample-time reward relabelling of a replay ring (csrc/relabel.hip) ------------------------------------------------
  * ONE launch for n int64 ring indices (all the minibatches of a `train` call): reward[idx[i]] = the reward net's
  * processed prediction of ring row idx[i]:
