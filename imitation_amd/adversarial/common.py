@@ -235,10 +235,10 @@ class AdversarialTrainer(abc.ABC):
         self._gen_replay_buffer = ring_cls(gen_replay_buffer_capacity, self.venv, device=self._device)
         # off-policy generators (DQN, TD3, DDPG) under a state-holder reward net: one `ia_offpolicy_step` launch per
         # environment step relabels the step and stores it to the learner's ring and to a per-round device tile
-        # (`dqn.RewardStepSource`); every other combination keeps the per-step host path of the wrapper
+        # (`step_source.RewardStepSource`); every other combination keeps the per-step host path of the wrapper
         self._step_source = None
         if self._frame_path or self._offpolicy_fused_ok():
-            # (the frame path: the same step for a uint8 frame ring under a CnnRewardNet, `dqn.FrameRewardStepSource`)
+            # (the frame path: the same step for a uint8 frame ring under a CnnRewardNet, `step_source.FrameRewardStepSource`)
             source_cls = dqn.FrameRewardStepSource if self._frame_path else dqn.RewardStepSource
             self._step_source = source_cls(self.gen_algo.replay_buffer, self.reward_train,
                                            tile_steps=self._round_steps_bound())

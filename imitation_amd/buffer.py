@@ -195,7 +195,7 @@ class FrameReplayBuffer(ReplayBuffer):
     """`ReplayBuffer` over a uint8 image space as a uint8 table: `obs` / `next_obs` uint8 `[capacity, C*H*W]`, the frames
     as the environment hands them over (a quarter of the float32 ring's bytes), discrete actions int64, dones uint8. The
     same draws from NumPy's global generator and the same index arithmetic as `ReplayBuffer`; `store_from_rollout` moves
-    the round tile of `dqn.FrameRewardStepSource` into the ring with one `ia_gather_frame_rows` launch
+    the round tile of `step_source.FrameRewardStepSource` into the ring with one `ia_gather_frame_rows` launch
     (csrc/offpolicy_frames.hip), which wraps at the capacity itself."""
 
     def __init__(self, capacity: int, venv=None, *, obs_shape=None, act_shape=None, obs_dtype=None, act_dtype=None,
@@ -237,7 +237,7 @@ class FrameReplayBuffer(ReplayBuffer):
         self._dones[lo:hi].copy_(th.from_numpy(np.ascontiguousarray(dones, dtype=np.uint8)))
 
     def store_from_rollout(self, rb, order: np.ndarray, truncate_ok: bool = True, infos=None) -> None:
-        """`store` for transitions in a uint8 round tile `rb` (`dqn.FrameRewardStepSource.rollout_view`): rows `order`
+        """`store` for transitions in a uint8 round tile `rb` (`step_source.FrameRewardStepSource.rollout_view`): rows `order`
         gathered device-to-device into the ring; same index arithmetic as `ReplayBuffer.store_from_rollout`."""
         from imitation_amd import _lib as L
         n = len(order)

@@ -1,6 +1,7 @@
-"""What SQIL needs of stable-baselines3's DQN (`algorithms/sqil.py:12-19,77-83`): `DQN`, `DQNPolicy` ("MlpPolicy"),
-`QNetwork`, SB3's `ReplayBuffer` and the off-policy loop -- a restatement of stable-baselines3 2.2.x from its documented
-behaviour ([SB3 dqn/dqn.py, dqn/policies.py, common/off_policy_algorithm.py, common/buffers.py]).
+"""What SQIL needs of stable-baselines3's DQN (`algorithms/sqil.py:12-19,77-83`): `DQN`, `DQNPolicy` ("MlpPolicy",
+"CnnPolicy") and `QNetwork` -- a restatement of stable-baselines3 2.2.x from its documented behaviour ([SB3 dqn/dqn.py,
+dqn/policies.py]). SB3's `ReplayBuffer` and the off-policy loop are `imitation_amd/off_policy.py`, the per-step reward
+sources of a learner ring under a learned reward `imitation_amd/step_source.py`; their names stay importable from here.
 
 Layout, as everywhere in this package: every index decision (ring position, sampled rows, exploration
 coin, random actions) is made on the host with SB3's own draw sequence from NumPy's GLOBAL stream; the learner ring and
@@ -18,26 +19,24 @@ route, `DQNPolicy.update_frames`, assembles each step's minibatch with one `ia_d
 """
 from __future__ import annotations
 
-import collections
-import copy
 import ctypes as C
 import os
-import sys
-import time
 import warnings
-from typing import Any, Dict, List, NamedTuple, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch as th
 from torch import nn
 
 from imitation_amd import _lib as L
-from imitation_amd import logger as imit_logger
 from imitation_amd import spaces
 from imitation_amd.cnn_policy import NatureCNN, NatureCnnTrunk, _is_image_space
 from imitation_amd.networks import require_device
+from imitation_amd.off_policy import (OffPolicyAlgorithm, ReplayBuffer, ReplayBufferSamples, ReplayIndex,  # noqa: F401
+                                      _device, _Table, adam_kwargs, table_pointers)
 from imitation_amd.policies import FlattenExtractor
-from imitation_amd.ppo import _CallbackList, _NullCallback, _schedule, set_random_seed
+from imitation_amd.step_source import (FrameRewardStepSource, RewardStepSource, StepSource, _RoundTile,  # noqa: F401
+                                       frame_reward_plan)
 
 
 def fused_enabled() -> bool:
@@ -54,517 +53,6 @@ def get_linear_fn(start: float, end: float, end_fraction: float):
         return start + (1 - progress_remaining) * (end - start) / end_fraction
 
     return func
-
-
-class ReplayBufferSamples(NamedTuple):
-    """[SB3 type_aliases.ReplayBufferSamples]"""
-    observations: th.Tensor
-    actions: th.Tensor
-    next_observations: th.Tensor
-    dones: th.Tensor
-    rewards: th.Tensor
-
-
-class ReplayIndex:
-    """The index logic of [SB3 buffers.ReplayBuffer], host only (no tensor, no GPU): a ring of
-    `max(buffer_size // n_envs, 1)` positions of `n_envs` rows each; `add` returns the position it wrote and wraps;
-    `sample` makes SB3's two draws from NumPy's GLOBAL stream (`np.random.randint(0, upper, size=b)`, then
-    `np.random.randint(0, high=n_envs, size=(b,))`); the row of (position, env) in a flat table is
-    `position * n_envs + env`."""
-
-    def __init__(self, buffer_size: int, n_envs: int = 1):
-        self.n_envs = int(n_envs)
-        self.buffer_size = max(int(buffer_size) // self.n_envs, 1)
-        self.pos = 0
-        self.full = False
-
-    def size(self) -> int:
-        return self.buffer_size if self.full else self.pos
-
-    def add(self) -> int:
-        at = self.pos
-        self.pos += 1
-        if self.pos == self.buffer_size:
-            self.full = True
-            self.pos = 0
-        return at
-
-    def fill(self) -> None:
-        """The state after `buffer_size` adds (the expert table: one add per demonstration)."""
-        self.pos, self.full = 0, True
-
-    def sample(self, batch_size: int) -> Tuple[np.ndarray, np.ndarray]:
-        upper_bound = self.buffer_size if self.full else self.pos
-        batch_inds = np.random.randint(0, upper_bound, size=batch_size)
-        env_indices = np.random.randint(0, high=self.n_envs, size=(len(batch_inds),))
-        return batch_inds, env_indices
-
-    def rows(self, batch_inds: np.ndarray, env_indices: np.ndarray) -> np.ndarray:
-        return batch_inds.astype(np.int64) * self.n_envs + env_indices.astype(np.int64)
-
-
-class _Table:
-    """Flat device table of transitions: obs / next_obs [N, D] float32 -- or uint8 for an image space (`frames`: D = C*H*W
-    bytes per row, the frames as the environment hands them over) --, action int64 [N] (Discrete) or float32 [N, A]
-    (Box, `act_dim` = A), reward, done float32 [N]."""
-
-    def __init__(self, rows: int, obs_dim: int, device, act_dim: Optional[int] = None, frames: bool = False):
-        self.rows, self.obs_dim, self.act_dim, self.frames = int(rows), int(obs_dim), act_dim, bool(frames)
-        self.obs_np = np.uint8 if self.frames else np.float32
-        obs_dtype = th.uint8 if self.frames else th.float32
-        self.obs = th.zeros(self.rows, obs_dim, dtype=obs_dtype, device=device)
-        self.next_obs = th.zeros(self.rows, obs_dim, dtype=obs_dtype, device=device)
-        if act_dim is None:
-            self.action = th.zeros(self.rows, dtype=th.int64, device=device)
-        else:
-            self.action = th.zeros(self.rows, int(act_dim), device=device)
-        self.reward = th.zeros(self.rows, device=device)
-        self.done = th.zeros(self.rows, device=device)
-
-    def write(self, lo: int, obs, next_obs, action, reward, done) -> None:
-        n = len(obs)
-        act = (np.int64, (n,)) if self.act_dim is None else (np.float32, (n, self.act_dim))
-        if self.frames and not (np.asarray(obs).dtype == np.uint8 and np.asarray(next_obs).dtype == np.uint8):
-            raise ValueError("a frame table stores uint8 frames as they come: the observations must be uint8 arrays")
-        for dst, src, dtype, shape in ((self.obs, obs, self.obs_np, (n, -1)), (self.next_obs, next_obs, self.obs_np, (n, -1)),
-                                       (self.action, action) + act, (self.reward, reward, np.float32, (n,)),
-                                       (self.done, done, np.float32, (n,))):
-            dst[lo:lo + n].copy_(th.from_numpy(np.array(src, dtype).reshape(shape)))
-
-
-def _device(device) -> th.device:
-    return th.device("cuda" if device == "auto" else device)
-
-
-class ReplayBuffer:
-    """[SB3 buffers.ReplayBuffer] for flat Box observations (float32 rows) or uint8 image observations (uint8 rows of
-    C*H*W bytes, `frames`) and Discrete or flat Box actions, its rows in device memory.
-    `handle_timeout_termination`: a `done` that is a time-limit truncation does not cut the bootstrap (the product
-    `done * (1 - timeout)` SB3 forms when sampling is formed when the row is stored)."""
-
-    def __init__(self, buffer_size: int, observation_space, action_space, device="auto", n_envs: int = 1,
-                 optimize_memory_usage: bool = False, handle_timeout_termination: bool = True):
-        if optimize_memory_usage:
-            raise NotImplementedError("optimize_memory_usage is not implemented")
-        if not isinstance(observation_space, spaces.Box) or not isinstance(action_space, (spaces.Discrete, spaces.Box)):
-            raise NotImplementedError("the replay buffer holds flat Box observations and Discrete or Box actions")
-        self.observation_space, self.action_space = observation_space, action_space
-        self.obs_dim = int(np.prod(observation_space.shape))
-        # Box actions: a float32 [rows, A] column; Discrete: the int64 [rows] column
-        self.act_dim = int(np.prod(action_space.shape)) if isinstance(action_space, spaces.Box) else None
-        self.device = _device(device)
-        self.n_envs = int(n_envs)
-        self.index = ReplayIndex(buffer_size, n_envs)
-        self.buffer_size = self.index.buffer_size
-        self.handle_timeout_termination = handle_timeout_termination
-        # an image space's frames stay uint8 end to end: uint8 [rows, C*H*W] tables, no float round trip
-        self.frames = _is_image_space(observation_space)
-        self.table = _Table(self.buffer_size * self.n_envs, self.obs_dim, self.device, self.act_dim, frames=self.frames)
-        # `RewardStepSource`: `add` then ignores its `reward` and stores the step with one `ia_offpolicy_step` launch
-        self.reward_source: Optional["RewardStepSource"] = None
-
-    @property
-    def pos(self) -> int:
-        return self.index.pos
-
-    @property
-    def full(self) -> bool:
-        return self.index.full
-
-    def size(self) -> int:
-        return self.index.size()
-
-    def add(self, obs, next_obs, action, reward, done, infos) -> None:
-        done = np.asarray(done, np.float32).reshape(-1)
-        if self.handle_timeout_termination:
-            timeouts = np.array([info.get("TimeLimit.truncated", False) for info in infos], np.float32)
-            done = done * (1 - timeouts)
-        if self.reward_source is not None:
-            self.reward_source.require_staged()   # (before the ring position moves)
-            self.reward_source.store_step(self.index.add() * self.n_envs, obs, next_obs, action, done)
-            return
-        reward = np.array(np.broadcast_to(np.asarray(reward, np.float32), (self.n_envs,)))
-        at = self.index.add()
-        self.table.write(at * self.n_envs, obs, next_obs, action, reward, done)
-
-    def sample_rows(self, batch_size: int) -> Tuple[np.ndarray, int]:
-        """The flat rows of one minibatch and how many of them (the first) index the learner ring: all here."""
-        return self.index.rows(*self.index.sample(batch_size)), batch_size
-
-    def expert_table(self) -> Optional[_Table]:
-        return None
-
-    def _gather(self, table: _Table, rows: np.ndarray) -> ReplayBufferSamples:
-        idx = th.from_numpy(rows).to(self.device)
-        obs, next_obs = table.obs[idx], table.next_obs[idx]
-        if self.frames:   # (uint8 [b, C, H, W], as SB3's buffer returns them)
-            shape = (-1,) + tuple(self.observation_space.shape)
-            obs, next_obs = obs.reshape(shape), next_obs.reshape(shape)
-        return ReplayBufferSamples(obs, table.action[idx].reshape(-1, table.act_dim or 1), next_obs,
-                                   table.done[idx].reshape(-1, 1), table.reward[idx].reshape(-1, 1))
-
-    def sample(self, batch_size: int, env=None) -> ReplayBufferSamples:
-        """[SB3 ReplayBuffer.sample] as tensors (the training loop itself passes `sample_rows` to the kernels)."""
-        if env is not None:
-            raise NotImplementedError("VecNormalize is not implemented")
-        rows, _ = ReplayBuffer.sample_rows(self, batch_size)
-        return self._gather(self.table, rows)
-
-
-class RewardStepSource:
-    """The reward source of a learner ring under a learned reward (`AdversarialTrainer` installs it on
-    `ReplayBuffer.reward_source`): one `ia_offpolicy_step` launch per environment step (csrc/offpolicy.hip) relabels the
-    step's rows and writes them to the ring, to a per-round device tile (what the trainer's own replay ring is filled
-    from) and to a pinned host tile of rewards (the wrapper's episode bookkeeping), instead of a reward prediction with
-    its read-back followed by five small copies.
-
-    The step's rows go in through a ring of `SLOTS` pinned host records; a record is rewritten only after the launch that
-    read it has completed (one event per record, waited on only when the ring of records wraps). `RewardVecEnvWrapper`
-    stages the action the environment saw and the raw dones (`stage`); `ReplayBuffer.add` passes the learner's view of the
-    step (`store_step`). With a net whose `forward_plan` the kernel covers the reward is computed in the launch; any other
-    net's `predict_th` stays on the device and the launch reads it from there."""
-
-    SLOTS = 8
-
-    def __init__(self, ring: "ReplayBuffer", reward_net, slots: Optional[int] = None, tile_steps: int = 64):
-        if ring.frames:
-            raise NotImplementedError("a learned reward on a uint8 frame ring is not implemented (ia_offpolicy_step reads "
-                                      "and writes float32 rows)")
-        self.ring, self.net = ring, reward_net
-        self.device = ring.device
-        self.n, self.od = ring.n_envs, ring.obs_dim
-        self.discrete = ring.act_dim is None
-        self.A = 1 if self.discrete else ring.act_dim
-        lib = L.load()
-        plan = reward_net.forward_plan()
-        self.base, self.out_act = None, L.ACT_NONE
-        if plan is not None:
-            base, out_act = plan
-            if lib.ia_offpolicy_step_ok(C.byref(base.mlp.desc), base.obs_dim, base.act_dim, *[int(f) for f in base.flags]):
-                self.base, self.out_act = base, out_act
-        self.act_dim = self.base.act_dim if self.base is not None else self.A
-        n, od, A = self.n, self.od, self.A
-        pin = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype).pin_memory()
-        self.slots = []
-        for _ in range(int(slots or self.SLOTS)):
-            rec = dict(obs=pin(n, od), next_obs=pin(n, od), dones=pin(n, dtype=th.uint8), ring_done=pin(n),
-                       act=pin(n, dtype=th.int64) if self.discrete else pin(n, A),
-                       ring_act=None if self.discrete else pin(n, A))
-            rec["np"] = {k: v.numpy() for k, v in rec.items() if v is not None}
-            self.slots.append(rec)
-        self.events: List[Optional[th.cuda.Event]] = [None] * len(self.slots)
-        self.launches = 0          # `ia_offpolicy_step` calls so far (tests count them)
-        self._slot_checked = -1
-        self._staged = -1          # the `launches` count at the latest `stage`
-        self.event_waits = 0       # records found still in flight when the ring of records wrapped
-        self.tile_step = 0         # steps in the round tile
-        self._alloc_tile(int(tile_steps))
-        self._args: List[Any] = [None] * len(self.slots)   # per record: (key, `OffpolicyStepArgs` with its pointers filled in)
-
-    def _alloc_tile(self, steps: int) -> None:
-        n, od, dev = self.n, self.od, self.device
-        old = getattr(self, "tile_obs", None)
-        olds = (self.tile_obs, self.tile_next, self.tile_act, self.tile_dones, self.rewards_host) if old is not None else None
-        self.tile_cap = steps
-        self.tile_obs = th.zeros((steps + 1) * n, od, device=dev)   # (one spare row block: `store_from_rollout`'s view)
-        self.tile_next = th.zeros(steps * n, od, device=dev)
-        self.tile_act = (th.zeros(steps * n, dtype=th.int64, device=dev) if self.discrete
-                         else th.zeros(steps * n, self.A, device=dev))
-        self.tile_dones = th.zeros(steps * n, dtype=th.uint8, device=dev)
-        self.rewards_host = th.zeros(steps, n).pin_memory()
-        self.rewards_np = self.rewards_host.numpy()
-        if olds is not None:   # a longer round than any before: the written rows move over (rare; one synchronisation)
-            th.cuda.current_stream().synchronize()
-            for new, o in zip((self.tile_obs, self.tile_next, self.tile_act, self.tile_dones, self.rewards_host), olds):
-                m = min(len(o), len(new))
-                new[:m].copy_(o[:m])
-            th.cuda.current_stream().synchronize()
-
-    def reward_row(self) -> np.ndarray:
-        """The row of the pinned reward tile the NEXT stored step fills (valid once that launch has completed)."""
-        if self.tile_step == self.tile_cap:
-            self._alloc_tile(2 * self.tile_cap)
-        return self.rewards_np[self.tile_step]
-
-    def _slot(self):
-        k = self.launches % len(self.slots)
-        if self._slot_checked != self.launches:   # (once per step: `stage` and `store_step` fill the same record)
-            self._slot_checked = self.launches
-            ev = self.events[k]
-            if ev is not None and not ev.query():
-                self.event_waits += 1
-                ev.synchronize()
-        return k, self.slots[k]["np"]
-
-    def stage(self, actions, dones) -> None:
-        """The action the environment executed (what the discriminator sees) and the raw dones of the step."""
-        _, rec = self._slot()
-        rec["act"][...] = np.asarray(actions).reshape(rec["act"].shape)
-        rec["dones"][...] = np.asarray(dones).reshape(-1)
-        self._staged = self.launches
-
-    def require_staged(self) -> None:
-        """A step can be stored only behind its `stage`: the record's discriminator action and raw dones would otherwise be
-        those of an earlier step."""
-        if self._staged != self.launches:
-            raise RuntimeError("ReplayBuffer.add on a ring with a reward source needs the step staged by the "
-                               "RewardVecEnvWrapper the trainer built (stage() was not called for this step)")
-
-    def store_step(self, ring_row: int, obs, next_obs, ring_action, ring_done) -> None:
-        self.require_staged()
-        k, rec = self._slot()
-        n = self.n
-        rec["obs"][...] = np.asarray(obs).reshape(n, -1)
-        rec["next_obs"][...] = np.asarray(next_obs).reshape(n, -1)
-        rec["ring_done"][...] = ring_done
-        if not self.discrete:
-            rec["ring_act"][...] = np.asarray(ring_action).reshape(n, -1)
-        if self.tile_step == self.tile_cap:
-            self._alloc_tile(2 * self.tile_cap)
-        rewards_in = None
-        if self.base is None:   # any other net: its prediction stays on the device
-            so, sa = tuple(self.ring.observation_space.shape), tuple(self.ring.action_space.shape)
-            rewards_in = self.net.predict_th(rec["obs"].reshape((n,) + so), rec["act"].reshape((n,) + sa),
-                                             rec["next_obs"].reshape((n,) + so), rec["dones"].astype(bool)).contiguous()
-        a = self._slot_args(k)
-        if rewards_in is not None:
-            a.rewards_in = rewards_in.data_ptr()
-        a.ring_row, a.tile_row = int(ring_row), self.tile_step * n
-        a.rewards_host = self.rewards_host.data_ptr() + 4 * self.tile_step * n
-        L.check(L.load().ia_offpolicy_step(C.byref(a), L.stream()), "ia_offpolicy_step")
-        if self.events[k] is None:
-            self.events[k] = th.cuda.Event()
-        self.events[k].record()
-        self.last_event = self.events[k]
-        self.launches += 1
-        self.tile_step += 1
-
-    def _slot_args(self, k: int):
-        """The argument record of pinned record `k`; refilled when a buffer it points to has moved (a longer round tile,
-        a reward net moved to another device)."""
-        b = self.base
-        nrm = None if b is None else b.mlp.norm
-        key = (self.tile_obs.data_ptr(), None if b is None else b.mlp.flat.data_ptr(),
-               None if nrm is None else nrm.running_mean.data_ptr())
-        if self._args[k] is not None and self._args[k][0] == key:
-            return self._args[k][1]
-        slot, t, n, a = self.slots[k], self.ring.table, self.n, L.OffpolicyStepArgs()
-        a.obs, a.next_obs = slot["obs"].data_ptr(), slot["next_obs"].data_ptr()
-        a.act_i64 = slot["act"].data_ptr() if self.discrete else None
-        a.act_f32 = None if self.discrete else slot["act"].data_ptr()
-        a.ring_act_f32 = None if self.discrete else slot["ring_act"].data_ptr()
-        a.dones, a.ring_done = slot["dones"].data_ptr(), slot["ring_done"].data_ptr()
-        a.n, a.obs_dim, a.act_dim = n, self.od, self.act_dim
-        if b is not None:
-            a.use_state, a.use_action, a.use_next_state, a.use_done = (int(f) for f in b.flags)
-            a.desc, a.params = C.pointer(b.mlp.desc), b.mlp.flat.data_ptr()
-            a.norm_mean = None if nrm is None else nrm.running_mean.data_ptr()
-            a.norm_var = None if nrm is None else nrm.running_var.data_ptr()
-            a.norm_eps, a.out_act = (0.0 if nrm is None else float(nrm.eps)), self.out_act
-        a.ring_obs, a.ring_next_obs = t.obs.data_ptr(), t.next_obs.data_ptr()
-        a.ring_action_i64 = t.action.data_ptr() if self.discrete else None
-        a.ring_action_f32 = None if self.discrete else t.action.data_ptr()
-        a.ring_reward, a.ring_done_out, a.ring_rows = t.reward.data_ptr(), t.done.data_ptr(), t.rows
-        a.tile_obs, a.tile_next_obs = self.tile_obs.data_ptr(), self.tile_next.data_ptr()
-        a.tile_act_i64 = self.tile_act.data_ptr() if self.discrete else None
-        a.tile_act_f32 = None if self.discrete else self.tile_act.data_ptr()
-        a.tile_dones, a.tile_rows = self.tile_dones.data_ptr(), self.tile_cap * n
-        self._args[k] = (key, a)
-        return a
-
-    def wait(self) -> None:
-        """Until the latest launch has completed (its rewards are then in the pinned tile)."""
-        if self.launches:
-            self.last_event.synchronize()
-
-    def rollout_view(self):
-        """The round tile with the fields `buffer.ReplayBuffer.store_from_rollout` reads."""
-        T, n = self.tile_step, self.n
-        return _RoundTile(self.tile_obs[:(T + 1) * n], self.tile_next[:T * n], self.tile_act[:T * n].reshape(T * n, -1),
-                          self.tile_dones[:T * n], T, n)
-
-    def reset_tile(self) -> None:
-        self.tile_step = 0
-
-
-class _RoundTile(NamedTuple):
-    obs: th.Tensor
-    next_fixed: th.Tensor
-    clipped: th.Tensor
-    dones: th.Tensor
-    buffer_size: int
-    n_envs: int
-
-
-def frame_reward_plan(reward_net):
-    """(cnn_net, softplus) when `reward_net` is what the frame path's reward launch covers -- `modules.CnnRewardNet` over
-    channel-first frames with `normalize_images`, plain or under GAIL's `RewardNetFromDiscriminatorLogit` --, else None."""
-    from imitation_amd import modules
-    net, softplus = reward_net, False
-    if type(net) is modules.RewardNetFromDiscriminatorLogit:
-        net, softplus = net.base, True
-    if type(net) is not modules.CnnRewardNet or net.hwc_format or not net.normalize_images:
-        return None
-    return net, softplus
-
-
-class FrameRewardStepSource:
-    """`RewardStepSource` for a uint8 frame ring under a `modules.CnnRewardNet` (csrc/offpolicy_frames.hip): per environment
-    step ONE `ia_offpolicy_frames_step` launch reads the step's frames once from a pinned host record and writes them to the
-    learner's ring, to the uint8 round tile and, as channel-last fp32 through the byte table, to the reward CNN's input;
-    the CNN runs under `no_grad` (`forward_nhwc`, the convolution ops); ONE `ia_offpolicy_frames_reward` launch selects
-    the action's (and done's) output, applies GAIL's softplus and writes the rewards to the ring and to the pinned host
-    reward tile. Same surface, same ring of pinned records with one event per record as `RewardStepSource`."""
-
-    SLOTS = 8
-
-    def __init__(self, ring: "ReplayBuffer", reward_net, slots: Optional[int] = None, tile_steps: int = 64):
-        from imitation_amd import ops
-        if not ring.frames or ring.act_dim is not None:
-            raise TypeError("FrameRewardStepSource stores uint8 frames with Discrete actions (RewardStepSource stores "
-                            "float32 rows)")
-        require_device(ring.device)
-        plan = frame_reward_plan(reward_net)
-        if plan is None:
-            raise NotImplementedError("the frame path's reward launch covers modules.CnnRewardNet(hwc_format=False) with "
-                                      "normalize_images, plain or under GAIL's softplus; any other net takes the host path")
-        self.ring, self.net = ring, reward_net
-        self.cnn_net, self.softplus = plan
-        self.device = ring.device
-        self.n, self.od = ring.n_envs, ring.obs_dim
-        self.shape = tuple(ring.observation_space.shape)          # (C, H, W)
-        self.n_actions = int(ring.action_space.n)
-        c = self.cnn_net
-        self.S = int(c.use_state) + int(c.use_next_state)
-        self.n_out = (self.n_actions if c.use_action else 1) * (2 if c.use_done else 1)
-        self.lut = ops._byte_lut(self.device)
-        C_, H, W = self.shape
-        self.X = th.empty(self.n, H, W, C_ * self.S, device=self.device)
-        n, od = self.n, self.od
-        pin = lambda *shape, dtype=th.float32: th.zeros(*shape, dtype=dtype).pin_memory()
-        self.slots = []
-        for _ in range(int(slots or self.SLOTS)):
-            rec = dict(obs=pin(n, od, dtype=th.uint8), next_obs=pin(n, od, dtype=th.uint8), dones=pin(n, dtype=th.uint8),
-                       ring_done=pin(n), act=pin(n, dtype=th.int64))
-            rec["np"] = {k: v.numpy() for k, v in rec.items()}
-            self.slots.append(rec)
-        self.events: List[Optional[th.cuda.Event]] = [None] * len(self.slots)
-        self.launches = 0          # `ia_offpolicy_frames_step` calls so far (tests count them)
-        self.reward_launches = 0   # `ia_offpolicy_frames_reward` calls so far
-        self._slot_checked = -1
-        self._staged = -1
-        self.event_waits = 0
-        self.tile_step = 0
-        self._alloc_tile(int(tile_steps))
-        self._args: List[Any] = [None] * len(self.slots)
-
-    def _alloc_tile(self, steps: int) -> None:
-        n, od, dev = self.n, self.od, self.device
-        old = getattr(self, "tile_obs", None)
-        olds = (self.tile_obs, self.tile_next, self.tile_act, self.tile_dones, self.rewards_host) if old is not None else None
-        self.tile_cap = steps
-        self.tile_obs = th.zeros(steps * n, od, dtype=th.uint8, device=dev)
-        self.tile_next = th.zeros(steps * n, od, dtype=th.uint8, device=dev)
-        self.tile_act = th.zeros(steps * n, dtype=th.int64, device=dev)
-        self.tile_dones = th.zeros(steps * n, dtype=th.uint8, device=dev)
-        self.rewards_host = th.zeros(steps, n).pin_memory()
-        self.rewards_np = self.rewards_host.numpy()
-        if olds is not None:   # a longer round than any before: the written rows move over (rare; one synchronisation)
-            th.cuda.current_stream().synchronize()
-            for new, o in zip((self.tile_obs, self.tile_next, self.tile_act, self.tile_dones, self.rewards_host), olds):
-                m = min(len(o), len(new))
-                new[:m].copy_(o[:m])
-            th.cuda.current_stream().synchronize()
-
-    def reward_row(self) -> np.ndarray:
-        """The row of the pinned reward tile the NEXT stored step fills (valid once its reward launch has completed)."""
-        if self.tile_step == self.tile_cap:
-            self._alloc_tile(2 * self.tile_cap)
-        return self.rewards_np[self.tile_step]
-
-    def _slot(self):
-        k = self.launches % len(self.slots)
-        if self._slot_checked != self.launches:   # (once per step: `stage` and `store_step` fill the same record)
-            self._slot_checked = self.launches
-            ev = self.events[k]
-            if ev is not None and not ev.query():
-                self.event_waits += 1
-                ev.synchronize()
-        return k, self.slots[k]["np"]
-
-    def stage(self, actions, dones) -> None:
-        """The action the environment executed and the raw dones of the step."""
-        _, rec = self._slot()
-        rec["act"][...] = np.asarray(actions).reshape(rec["act"].shape)
-        rec["dones"][...] = np.asarray(dones).reshape(-1)
-        self._staged = self.launches
-
-    def require_staged(self) -> None:
-        if self._staged != self.launches:
-            raise RuntimeError("ReplayBuffer.add on a ring with a reward source needs the step staged by the "
-                               "RewardVecEnvWrapper the trainer built (stage() was not called for this step)")
-
-    def store_step(self, ring_row: int, obs, next_obs, ring_action, ring_done) -> None:
-        self.require_staged()
-        k, rec = self._slot()
-        n = self.n
-        obs, next_obs = np.asarray(obs), np.asarray(next_obs)
-        if obs.dtype != np.uint8 or next_obs.dtype != np.uint8:
-            raise ValueError("a frame table stores uint8 frames as they come: the observations must be uint8 arrays")
-        rec["obs"][...] = obs.reshape(n, -1)
-        rec["next_obs"][...] = next_obs.reshape(n, -1)
-        rec["ring_done"][...] = ring_done
-        if self.tile_step == self.tile_cap:
-            self._alloc_tile(2 * self.tile_cap)
-        a = self._slot_args(k)
-        a.ring_row, a.tile_row = int(ring_row), self.tile_step * n
-        a.rewards_host = self.rewards_host.data_ptr() + 4 * self.tile_step * n
-        lib, st = L.load(), L.stream()
-        L.check(lib.ia_offpolicy_frames_step(C.byref(a), st), "ia_offpolicy_frames_step")
-        with th.no_grad():
-            out = self.cnn_net.cnn.forward_nhwc(self.X).contiguous()
-        c = self.cnn_net
-        L.check(lib.ia_offpolicy_frames_reward(C.byref(a), out.data_ptr(), self.n_out, None, self.n_actions,
-                                               int(c.use_action), int(c.use_done), int(self.softplus), st),
-                "ia_offpolicy_frames_reward")
-        if self.events[k] is None:
-            self.events[k] = th.cuda.Event()
-        self.events[k].record()
-        self.last_event = self.events[k]
-        self.launches += 1
-        self.reward_launches += 1
-        self.tile_step += 1
-
-    def _slot_args(self, k: int):
-        """The argument record of pinned record `k`; refilled when the round tile has moved."""
-        key = self.tile_obs.data_ptr()
-        if self._args[k] is not None and self._args[k][0] == key:
-            return self._args[k][1]
-        slot, t, a = self.slots[k], self.ring.table, L.OffpolicyFramesArgs()
-        a.obs, a.next_obs, a.act = slot["obs"].data_ptr(), slot["next_obs"].data_ptr(), slot["act"].data_ptr()
-        a.dones, a.ring_done = slot["dones"].data_ptr(), slot["ring_done"].data_ptr()
-        a.n, (a.C, a.H, a.W) = self.n, self.shape
-        a.use_state, a.use_next_state = int(self.cnn_net.use_state), int(self.cnn_net.use_next_state)
-        a.lut, a.X = self.lut.data_ptr(), self.X.data_ptr()
-        a.ring_obs, a.ring_next_obs, a.ring_action = t.obs.data_ptr(), t.next_obs.data_ptr(), t.action.data_ptr()
-        a.ring_reward, a.ring_done_out, a.ring_rows = t.reward.data_ptr(), t.done.data_ptr(), t.rows
-        a.tile_obs, a.tile_next_obs = self.tile_obs.data_ptr(), self.tile_next.data_ptr()
-        a.tile_act, a.tile_dones, a.tile_rows = self.tile_act.data_ptr(), self.tile_dones.data_ptr(), self.tile_cap * self.n
-        self._args[k] = (key, a)
-        return a
-
-    def wait(self) -> None:
-        """Until the latest reward launch has completed (its rewards are then in the pinned tile)."""
-        if self.launches:
-            self.last_event.synchronize()
-
-    def rollout_view(self):
-        """The round tile with the fields `buffer.FrameReplayBuffer.store_from_rollout` reads."""
-        T, n = self.tile_step, self.n
-        return _RoundTile(self.tile_obs[:T * n], self.tile_next[:T * n], self.tile_act[:T * n], self.tile_dones[:T * n], T, n)
-
-    def reset_tile(self) -> None:
-        self.tile_step = 0
 
 
 class QNetwork:
@@ -749,10 +237,7 @@ class DQNPolicy:
                 raise NotImplementedError(f"features_extractor_kwargs {sorted(unknown)} are not implemented")
         self.net_arch = [] if self.frames else [64, 64] if net_arch is None else list(net_arch)
         self.activation_fn = activation_fn
-        self.optimizer_kwargs = dict(optimizer_kwargs or {})
-        unknown = set(self.optimizer_kwargs) - {"betas", "eps", "weight_decay"}
-        if unknown:
-            raise NotImplementedError(f"optimizer_kwargs {sorted(unknown)} are not implemented")
+        self.optimizer_kwargs, self.betas, self.eps, self.weight_decay = adam_kwargs(optimizer_kwargs)
         if self.frames:
             features_dim = int((features_extractor_kwargs or {}).get("features_dim", 512))
             self.q_net = CnnQNetwork(observation_space, action_space, features_dim)
@@ -762,9 +247,6 @@ class DQNPolicy:
             self.q_net_target = QNetwork(observation_space, action_space, self.net_arch, activation_fn)
         self.q_net_target._flat.copy_(self.q_net._flat)
         self.lr = float(lr_schedule(1))
-        self.betas = tuple(self.optimizer_kwargs.get("betas", (0.9, 0.999)))
-        self.eps = float(self.optimizer_kwargs.get("eps", 1e-8))
-        self.weight_decay = float(self.optimizer_kwargs.get("weight_decay", 0.0))
         self.exp_avg = th.zeros_like(self.q_net._flat)
         self.exp_avg_sq = th.zeros_like(self.q_net._flat)
         self.adam_steps = 0
@@ -865,14 +347,10 @@ class DQNPolicy:
         """`n_steps` gradient steps in one launch (`ia_dqn_update`); `idx_dev` int64 [n_steps, batch_size]."""
         q = self.q_net
         scal = np.ascontiguousarray(self._adam_scalars(lr, n_steps))
-        e = expert
-        rc = L.load().ia_dqn_update(
+        rc = L.load().ia_dqn_update(   # (the kernel takes no row counts: the five columns of each table)
             q.obs_dim, q.net_arch[0], q.n_actions, int(batch_size), int(n_new), int(n_steps), L.ptr(q._flat),
-            L.ptr(self.q_net_target._flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(ring.obs),
-            L.ptr(ring.next_obs), L.ptr(ring.action), L.ptr(ring.reward), L.ptr(ring.done),
-            None if e is None else L.ptr(e.obs), None if e is None else L.ptr(e.next_obs),
-            None if e is None else L.ptr(e.action), None if e is None else L.ptr(e.reward),
-            None if e is None else L.ptr(e.done), L.ptr(idx_dev), float(gamma), float(max_grad_norm), float(self.betas[0]),
+            L.ptr(self.q_net_target._flat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), *ring.pointers()[:5],
+            *table_pointers(expert)[:5], L.ptr(idx_dev), float(gamma), float(max_grad_norm), float(self.betas[0]),
             float(self.betas[1]), self.eps, scal.ctypes.data, L.ptr(stats), L.ptr(grad_out), L.stream())
         L.check(rc, "ia_dqn_update")
         self.adam_steps += n_steps
@@ -969,15 +447,13 @@ class DQNPolicy:
         q, qt, B, st = self.q_net, self.q_net_target, int(batch_size), L.stream()
         w = self._frames_ws(B)
         scal = self._adam_scalars(lr, n_steps)
-        n, D, e = q._flat.numel(), q.obs_dim, expert
+        n, D = q._flat.numel(), q.obs_dim
         shape = (B,) + tuple(self.observation_space.shape)
         obs, nxt = w["obs"].view(shape), w["nxt"].view(shape)
         idx_ptr, stats_ptr = idx_dev.data_ptr(), stats.data_ptr()
+        tables = ring.pointers() + table_pointers(expert)
         for s in range(n_steps):
-            L.call("ia_dqn_assemble_u8", L.ptr(ring.obs), L.ptr(ring.next_obs), L.ptr(ring.action), L.ptr(ring.reward),
-                   L.ptr(ring.done), ring.rows, None if e is None else L.ptr(e.obs), None if e is None else L.ptr(e.next_obs),
-                   None if e is None else L.ptr(e.action), None if e is None else L.ptr(e.reward),
-                   None if e is None else L.ptr(e.done), 0 if e is None else e.rows, idx_ptr + 8 * s * B, B, int(n_new), D,
+            L.call("ia_dqn_assemble_u8", *tables, idx_ptr + 8 * s * B, B, int(n_new), D,
                    L.ptr(w["obs"]), L.ptr(w["nxt"]), L.ptr(w["act"]), L.ptr(w["rew"]), L.ptr(w["done"]), st)
             d = q.forward(obs)
             dt = qt.forward(nxt)
@@ -1023,161 +499,6 @@ class CnnPolicy(DQNPolicy):
                          features_extractor_kwargs, normalize_images, optimizer_class, optimizer_kwargs)
 
 
-class OffPolicyAlgorithm:
-    """What [SB3 common/off_policy_algorithm.py] gives DQN and TD3 alike: the `BaseAlgorithm` surface, `learn`,
-    `collect_rollouts`, `_store_transition` and `_dump_logs`. A subclass supplies `_sample_action`, `_on_step`, `train`."""
-
-    # ---- SB3 BaseAlgorithm surface ----------------------------------------------------------------------------------
-    @property
-    def logger(self):
-        return self._logger
-
-    def set_logger(self, logger) -> None:
-        self._logger = logger
-        self._custom_logger = True
-
-    def get_env(self):
-        return self.env
-
-    def set_env(self, env, force_reset: bool = True) -> None:
-        """[SB3 BaseAlgorithm.set_env]: the spaces and the number of environments must be the model's; with `force_reset`
-        the next `_setup_learn` resets the environment."""
-        if env.num_envs != self.n_envs:
-            raise ValueError("The number of environments to be set is different from the number of environments in "
-                             f"the model: ({env.num_envs} != {self.n_envs})")
-        if env.observation_space != self.observation_space:
-            raise ValueError(f"Observation spaces do not match: {self.observation_space} != {env.observation_space}")
-        if env.action_space != self.action_space:
-            raise ValueError(f"Action spaces do not match: {self.action_space} != {env.action_space}")
-        if force_reset:
-            self._last_obs = None
-        self.n_envs = env.num_envs
-        self.env = env
-
-    def _init_callback(self, callback):
-        if callback is None:
-            callback = _NullCallback()
-        elif isinstance(callback, (list, tuple)):
-            callback = _CallbackList(callback)
-        callback.init_callback(self)
-        return callback
-
-    def _setup_learn(self, total_timesteps: int, callback, reset_num_timesteps: bool):
-        self.start_time = time.time_ns()
-        if self.ep_info_buffer is None or reset_num_timesteps:
-            self.ep_info_buffer = collections.deque(maxlen=self._stats_window_size)
-        if reset_num_timesteps:
-            self.num_timesteps = 0
-            self._episode_num = 0
-        else:
-            total_timesteps += self.num_timesteps
-        self._total_timesteps = total_timesteps
-        self._num_timesteps_at_start = self.num_timesteps
-        if reset_num_timesteps or self._last_obs is None:
-            self._last_obs = self.env.reset()
-            self._last_episode_starts = np.ones((self.env.num_envs,), dtype=bool)
-        if not self._custom_logger and self._logger is None:
-            self._logger = imit_logger.Logger(None, [])
-        return total_timesteps, self._init_callback(callback)
-
-    def _store_transition(self, buffer_action, new_obs, reward, dones, infos) -> None:
-        next_obs = copy.deepcopy(new_obs)
-        for i, done in enumerate(dones):
-            if done and infos[i].get("terminal_observation") is not None:
-                next_obs[i] = infos[i]["terminal_observation"]
-        self.replay_buffer.add(self._last_obs, next_obs, buffer_action, reward, dones, infos)
-        self._last_obs = new_obs
-
-    def _on_step(self) -> None:
-        pass
-
-    def _run_updates(self, rows: np.ndarray, idx_dev: th.Tensor, run) -> None:
-        """The gradient steps of one `train` call, `run(lo, hi)` being steps [lo, hi) of it, behind the sample-time reward
-        relabelling of a `ReplayBufferRewardWrapper` (imitation_amd/replay_buffer_wrapper.py): every sampled row of the
-        call relabelled on the device, then one `run` over all steps; or, for a `reward_fn` only the host can call, per
-        step its rows relabelled and that one step run. Any other buffer: `run(0, G)` as it stands."""
-        G = len(rows)
-        relabel = getattr(self.replay_buffer, "relabel_for_train", None)
-        if relabel is None or relabel(idx_dev):
-            run(0, G)
-            return
-        for s in range(G):
-            self.replay_buffer.relabel_step(rows[s], idx_dev[s])
-            run(s, s + 1)
-
-    def _on_episode_end(self, env_index: int, n_envs: int) -> None:
-        """[SB3 collect_rollouts]: where an episode's end resets the action noise."""
-
-    def _dump_logs(self) -> None:
-        elapsed = max((time.time_ns() - self.start_time) / 1e9, sys.float_info.epsilon)
-        fps = int((self.num_timesteps - self._num_timesteps_at_start) / elapsed)
-        self.logger.record("time/episodes", self._episode_num, exclude="tensorboard")
-        if len(self.ep_info_buffer) > 0 and len(self.ep_info_buffer[0]) > 0:
-            self.logger.record("rollout/ep_rew_mean", float(np.mean([e["r"] for e in self.ep_info_buffer])))
-            self.logger.record("rollout/ep_len_mean", float(np.mean([e["l"] for e in self.ep_info_buffer])))
-        self.logger.record("time/fps", fps)
-        self.logger.record("time/time_elapsed", int(elapsed), exclude="tensorboard")
-        self.logger.record("time/total_timesteps", self.num_timesteps, exclude="tensorboard")
-        self.logger.dump(step=self.num_timesteps)
-
-    def collect_rollouts(self, env, callback, train_freq, learning_starts: int, log_interval) -> Tuple[int, bool]:
-        """[SB3 OffPolicyAlgorithm.collect_rollouts] -> (timesteps collected, continue training). `train_freq`: a number of
-        steps, or SB3's pair (n, "step" | "episode"); episodes need one environment, as there."""
-        self.policy.set_training_mode(False)
-        steps, episodes = 0, 0
-        freq, unit = train_freq if isinstance(train_freq, tuple) else (train_freq, "step")
-        assert freq > 0, "Should at least collect one step or episode."
-        if env.num_envs > 1:
-            assert unit == "step", "You must use only one env when doing episodic training."
-        callback.on_rollout_start()
-        # [SB3 utils.should_collect_more_steps]
-        while (steps < freq) if unit == "step" else (episodes < freq):
-            actions = self._sample_action(learning_starts, env.num_envs)
-            # (a learner with continuous actions returns the pair (env action, buffer action))
-            actions, buffer_actions = actions if isinstance(actions, tuple) else (actions, actions)
-            new_obs, rewards, dones, infos = env.step(actions)
-            self.num_timesteps += env.num_envs
-            steps += 1
-            callback.update_locals(locals())
-            if not callback.on_step():
-                return steps * env.num_envs, False
-            for info in infos:
-                if info.get("episode") is not None:
-                    self.ep_info_buffer.extend([info["episode"]])
-            self._store_transition(buffer_actions, new_obs, rewards, dones, infos)
-            self._current_progress_remaining = 1.0 - float(self.num_timesteps) / float(self._total_timesteps)
-            self._on_step()
-            for i, done in enumerate(dones):
-                if done:
-                    episodes += 1
-                    self._episode_num += 1
-                    self._on_episode_end(i, env.num_envs)
-                    if log_interval is not None and self._episode_num % log_interval == 0:
-                        self._dump_logs()
-        callback.on_rollout_end()
-        return steps * env.num_envs, True
-
-    def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "DQN",
-              reset_num_timesteps: bool = True, progress_bar: bool = False):
-        if progress_bar:
-            raise NotImplementedError("the progress bar is not implemented")
-        require_device(self.device)
-        total_timesteps, callback = self._setup_learn(total_timesteps, callback, reset_num_timesteps)
-        callback.on_training_start(locals(), globals())
-        while self.num_timesteps < total_timesteps:
-            collected, go_on = self.collect_rollouts(self.env, callback, self.train_freq, self.learning_starts, log_interval)
-            if not go_on:
-                break
-            if self.num_timesteps > 0 and self.num_timesteps > self.learning_starts:
-                gradient_steps = self.gradient_steps if self.gradient_steps >= 0 else collected
-                if gradient_steps > 0:
-                    self.train(batch_size=self.batch_size, gradient_steps=gradient_steps)
-        callback.on_training_end()
-        return self
-
-
-
-
 class DQN(OffPolicyAlgorithm):
     """[SB3 dqn.DQN] with `train_freq` in steps."""
 
@@ -1191,68 +512,29 @@ class DQN(OffPolicyAlgorithm):
                  exploration_final_eps: float = 0.05, max_grad_norm: float = 10, stats_window_size: int = 100,
                  tensorboard_log=None, policy_kwargs: Optional[Dict[str, Any]] = None, verbose: int = 0,
                  seed: Optional[int] = None, device="auto", _init_setup_model: bool = True):
-        if isinstance(policy, str):
-            if policy not in self.policy_aliases:
-                raise NotImplementedError(f"policy {policy!r}: only 'MlpPolicy' and 'CnnPolicy' are implemented for DQN")
-            policy = self.policy_aliases[policy]
+        if isinstance(policy, str) and policy not in self.policy_aliases:
+            raise NotImplementedError(f"policy {policy!r}: only 'MlpPolicy' and 'CnnPolicy' are implemented for DQN")
         if isinstance(train_freq, tuple):
             if len(train_freq) != 2 or train_freq[1] != "step":
                 raise NotImplementedError("train_freq is counted in steps")
             train_freq = train_freq[0]
         if tensorboard_log is not None:
             raise NotImplementedError("tensorboard logging is not implemented")
-        self.policy_class = policy
-        self.policy_kwargs = dict(policy_kwargs or {})
-        self.device = _device(device)
-        self.learning_rate, self.buffer_size, self.learning_starts = learning_rate, buffer_size, learning_starts
-        self.batch_size, self.tau, self.gamma = batch_size, tau, gamma
-        self.train_freq, self.gradient_steps = int(train_freq), gradient_steps
-        self.replay_buffer_class = replay_buffer_class
-        self.replay_buffer_kwargs = dict(replay_buffer_kwargs or {})
-        self.optimize_memory_usage = optimize_memory_usage
-        self.target_update_interval = target_update_interval
+        super().__init__(policy=policy, env=env, learning_rate=learning_rate, buffer_size=buffer_size,
+                         learning_starts=learning_starts, batch_size=batch_size, tau=tau, gamma=gamma,
+                         train_freq=int(train_freq), gradient_steps=gradient_steps, replay_buffer_class=replay_buffer_class,
+                         replay_buffer_kwargs=replay_buffer_kwargs, optimize_memory_usage=optimize_memory_usage,
+                         stats_window_size=stats_window_size, policy_kwargs=policy_kwargs, verbose=verbose, seed=seed,
+                         device=device)
+        self.target_update_interval, self.max_grad_norm = target_update_interval, max_grad_norm
         self.exploration_initial_eps, self.exploration_final_eps = exploration_initial_eps, exploration_final_eps
         self.exploration_fraction = exploration_fraction
-        self.max_grad_norm, self.seed, self.verbose = max_grad_norm, seed, verbose
         self._n_calls = 0
         self.exploration_rate = 0.0   # [SB3 dqn.py]: zero until the first `_on_step`
-        self.num_timesteps = 0
-        self._total_timesteps = 0
-        self._num_timesteps_at_start = 0
-        self._n_updates = 0
-        self._episode_num = 0
-        self._current_progress_remaining = 1.0
-        self._last_obs = None
-        self._last_episode_starts = None
-        self._stats_window_size = stats_window_size
-        self.ep_info_buffer = None
-        self._logger: Optional[imit_logger.Logger] = None
-        self._custom_logger = False
-        self.start_time = 0
-        self.env = env
-        self.policy: Optional[DQNPolicy] = None
-        self.replay_buffer: Optional[ReplayBuffer] = None
-        self.last_action_branch: Optional[str] = None   # "warmup" / "explore" / "greedy" of the latest `_sample_action`
-        if env is not None:
-            self.observation_space, self.action_space, self.n_envs = env.observation_space, env.action_space, env.num_envs
         if _init_setup_model:
             self._setup_model()
 
-    def _setup_model(self) -> None:
-        self.lr_schedule = _schedule(self.learning_rate)
-        if self.seed is not None:
-            set_random_seed(self.seed)
-            self.action_space.seed(self.seed)
-            if self.env is not None:
-                self.env.seed(self.seed)
-        if self.replay_buffer_class is None:
-            self.replay_buffer_class = ReplayBuffer
-        if self.replay_buffer is None:
-            self.replay_buffer = self.replay_buffer_class(
-                self.buffer_size, self.observation_space, self.action_space, device=self.device, n_envs=self.n_envs,
-                optimize_memory_usage=self.optimize_memory_usage, **self.replay_buffer_kwargs)
-        self.policy = self.policy_class(self.observation_space, self.action_space, self.lr_schedule,
-                                        **self.policy_kwargs).to(self.device)
+    def _bind_policy(self) -> None:
         self.q_net, self.q_net_target = self.policy.q_net, self.policy.q_net_target
         self.exploration_schedule = get_linear_fn(self.exploration_initial_eps, self.exploration_final_eps,
                                                   self.exploration_fraction)
@@ -1289,20 +571,14 @@ class DQN(OffPolicyAlgorithm):
         self.exploration_rate = self.exploration_schedule(self._current_progress_remaining)
         self.logger.record("rollout/exploration_rate", self.exploration_rate)
 
+    def _check_rows(self, rows: np.ndarray, n_new: int) -> None:
+        if self.policy.frames:   # (the assemble kernel moves whole frames by these indices: checked before any launch)
+            self.policy.check_rows(rows, n_new, self.replay_buffer.table, self.replay_buffer.expert_table())
+
     def train(self, gradient_steps: int, batch_size: int = 100) -> None:
         """[SB3 DQN.train]: the index draws of all `gradient_steps` minibatches first (the same global-stream draws in
         the same order: nothing else draws in between), one upload, the update, one read-back."""
-        self.policy.set_training_mode(True)
-        lr = self.lr_schedule(self._current_progress_remaining)
-        self.logger.record("train/learning_rate", lr)
-        rows = np.empty((gradient_steps, batch_size), np.int64)
-        n_new = batch_size
-        for s in range(gradient_steps):
-            rows[s], n_new = self.replay_buffer.sample_rows(batch_size)
-        self.last_sample_rows, self.last_n_new = rows, n_new
-        if self.policy.frames:   # (the assemble kernel moves whole frames by these indices: checked before any launch)
-            self.policy.check_rows(rows, n_new, self.replay_buffer.table, self.replay_buffer.expert_table())
-        idx_dev = th.from_numpy(rows).to(self.device)
+        lr, rows, n_new, idx_dev = self._begin_train(gradient_steps, batch_size)
         stats = th.empty(gradient_steps, 2, device=self.device)
         self._run_updates(rows, idx_dev, lambda lo, hi: self.policy.update(
             self.replay_buffer.table, self.replay_buffer.expert_table(), idx_dev[lo:hi], n_new, hi - lo, batch_size,

@@ -87,6 +87,8 @@ class _TableView:
         self.obs, self.next_obs, self.action, self.done = inner.obs, inner.next_obs, inner.action, inner.done
         self.reward = reward
 
+    pointers = _Table.pointers
+
 
 class ReplayBufferRewardWrapper(ReplayBuffer):
     """Relabel the rewards in transitions sampled from a `ReplayBuffer` (`policies/replay_buffer_wrapper.py:26-103`)."""

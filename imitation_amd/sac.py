@@ -28,11 +28,11 @@ import torch as th
 from torch import nn
 
 from imitation_amd import _lib as L
-from imitation_amd.dqn import ReplayBuffer, _Table
 from imitation_amd.networks import require_device
+from imitation_amd.off_policy import _Table
 from imitation_amd.policies import FlattenExtractor
-from imitation_amd.ppo import _schedule, set_random_seed
-from imitation_amd.td3 import TD3, ContinuousCritic, _check_spaces, _Holder, _Stack, create_mlp, get_actor_critic_arch
+from imitation_amd.td3 import (ContinuousCritic, ContinuousOffPolicyAlgorithm, ContinuousPolicy, _check_spaces, _Holder,
+                               _Stack, create_mlp)
 
 LOG_STD_MAX, LOG_STD_MIN = 2, -20   # [SB3 sac/policies.py]
 
@@ -108,11 +108,13 @@ class Actor(_Holder):
         return a, logp
 
 
-class SACPolicy:
+class SACPolicy(ContinuousPolicy):
     """[SB3 sac.policies.SACPolicy]: `_build` makes the actor, the critic and the critic target (which loads the critic's
     state), in that order; there is no actor target. One Adam over the actor and one over the critic; the entropy
     coefficient and its optimiser belong to the algorithm in SB3 and are set up here by `SAC._setup_model`
     (`setup_ent_coef`), next to the buffers the step kernels read."""
+
+    holders = ("actor", "critic", "critic_target")
 
     def __init__(self, observation_space, action_space, lr_schedule, net_arch=None, activation_fn=nn.ReLU,
                  use_sde: bool = False, log_std_init: float = -3, use_expln: bool = False, clip_mean: float = 2.0,
@@ -121,45 +123,20 @@ class SACPolicy:
                  share_features_extractor: bool = False):
         if use_sde:
             raise NotImplementedError("gSDE is not implemented")
-        if features_extractor_class is not FlattenExtractor:
-            raise NotImplementedError("only the flatten extractor (MlpPolicy) is implemented: no CNN extractor")
-        if share_features_extractor:
-            raise NotImplementedError("share_features_extractor=True is not implemented")
-        if optimizer_class is not th.optim.Adam:
-            raise NotImplementedError("only torch.optim.Adam is implemented")
-        self.observation_space, self.action_space = observation_space, action_space
-        self.net_arch = [256, 256] if net_arch is None else net_arch
-        actor_arch, critic_arch = get_actor_critic_arch(self.net_arch)
-        self.activation_fn, self.n_critics = activation_fn, n_critics
-        self.optimizer_kwargs = dict(optimizer_kwargs or {})
-        unknown = set(self.optimizer_kwargs) - {"betas", "eps", "weight_decay"}
-        if unknown:
-            raise NotImplementedError(f"optimizer_kwargs {sorted(unknown)} are not implemented")
-        # [SB3 SACPolicy._build]: the draw order of torch's global generator
-        self.actor = Actor(observation_space, action_space, actor_arch, activation_fn)
-        self.critic = ContinuousCritic(observation_space, action_space, critic_arch, activation_fn, n_critics)
-        self.critic_target = ContinuousCritic(observation_space, action_space, critic_arch, activation_fn, n_critics)
-        # online parameters as ONE flat buffer [actor | critic] (one pair of moment buffers); the target is the critic's
-        self._online = th.cat([self.actor._init_flat(), self.critic._init_flat()]).contiguous()
-        self._target = self.critic._init_flat().clone().contiguous()
-        self.exp_avg, self.exp_avg_sq = th.zeros_like(self._online), th.zeros_like(self._online)
-        self.lr = float(lr_schedule(1))
-        self.betas = tuple(self.optimizer_kwargs.get("betas", (0.9, 0.999)))
-        self.eps = float(self.optimizer_kwargs.get("eps", 1e-8))
-        self.weight_decay = float(self.optimizer_kwargs.get("weight_decay", 0.0))
-        self.actor_adam_steps = self.critic_adam_steps = self.ent_adam_steps = 0
-        self.training = True
-        self.squash_output = True
+        super().__init__(observation_space, action_space, lr_schedule, [256, 256] if net_arch is None else net_arch,
+                         activation_fn, features_extractor_class, optimizer_class, optimizer_kwargs, n_critics,
+                         share_features_extractor)
         # the entropy coefficient: [log_ent_coef, exp_avg, exp_avg_sq, alpha slot] as one device buffer
+        self.ent_adam_steps = 0
         self.ent_learned = False
         self.ent_state = th.zeros(4)
-        self._ws: Dict[Any, Any] = {}
-        self._bind()
 
-    def _bind(self) -> None:
-        na = self.actor.numel()
-        self.actor._flat, self.critic._flat = self._online[:na], self._online[na:]
-        self.critic_target._flat = self._target
+    def _build(self, actor_arch: List[int], critic_arch: List[int]) -> None:
+        # [SB3 SACPolicy._build]
+        space, fn = (self.observation_space, self.action_space), self.activation_fn
+        self.actor = Actor(*space, actor_arch, fn)
+        self.critic = ContinuousCritic(*space, critic_arch, fn, self.n_critics)
+        self.critic_target = ContinuousCritic(*space, critic_arch, fn, self.n_critics)
 
     def setup_ent_coef(self, learned: bool, init_value: float) -> None:
         """Learned: `log_ent_coef = log(ones(1) * init)` with fresh Adam moments; constant: the slot holds the value."""
@@ -177,34 +154,9 @@ class SACPolicy:
     def log_ent_coef(self) -> Optional[th.Tensor]:
         return self.ent_state[0:1] if self.ent_learned else None
 
-    @property
-    def device(self) -> th.device:
-        return self._online.device
-
     def to(self, device):
-        self._online, self._target = self._online.to(device).contiguous(), self._target.to(device).contiguous()
-        self.exp_avg, self.exp_avg_sq = self.exp_avg.to(device), self.exp_avg_sq.to(device)
         self.ent_state = self.ent_state.to(device)
-        self._ws = {}
-        self._bind()
-        return self
-
-    def set_training_mode(self, mode: bool) -> None:
-        self.training = mode
-
-    def parameters(self):
-        for h in (self.actor, self.critic, self.critic_target):
-            yield from h.parameters()
-
-    def state_dict(self) -> Dict[str, th.Tensor]:
-        out: Dict[str, th.Tensor] = {}
-        for name in ("actor", "critic", "critic_target"):
-            out.update({f"{name}.{k}": v for k, v in getattr(self, name).state_dict().items()})
-        return out
-
-    def load_state_dict(self, sd) -> None:
-        for name in ("actor", "critic", "critic_target"):
-            getattr(self, name).load_state_dict({k[len(name) + 1:]: v for k, v in sd.items() if k.startswith(name + ".")})
+        return super().to(device)
 
     def optimizer_state(self) -> Dict[str, th.Tensor]:
         """Adam's moments per optimiser in the order of SB3's `parameters()` (the actor's are gathered out of the fused
@@ -218,14 +170,6 @@ class SACPolicy:
         return out
 
     # ---- [SB3 BasePolicy] actions ------------------------------------------------------------------------------------
-    def scale_action(self, action: np.ndarray) -> np.ndarray:
-        low, high = self.action_space.low, self.action_space.high
-        return 2.0 * ((action - low) / (high - low)) - 1.0
-
-    def unscale_action(self, scaled_action: np.ndarray) -> np.ndarray:
-        low, high = self.action_space.low, self.action_space.high
-        return low + (0.5 * (scaled_action + 1.0) * (high - low))
-
     def actor_output(self, observation: np.ndarray, deterministic: bool = False) -> np.ndarray:
         """The squashed action of host observations (one upload of [obs], one of eps, one read-back): `tanh(mu)` when
         `deterministic`, else one [n, A] draw from torch's global generator, as [SB3 Actor.forward] makes."""
@@ -238,45 +182,14 @@ class SACPolicy:
         a, _ = self.actor.action_log_prob(th.from_numpy(obs).to(self.device), eps)
         return a.cpu().numpy()
 
-    def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
-        """[SB3 BasePolicy.predict] of a squashing policy: the actor's action, unscaled to the action bounds."""
-        self.set_training_mode(False)
-        observation = np.asarray(observation)
-        vectorized = observation.shape != tuple(self.observation_space.shape)
-        actions = self.actor_output(observation, deterministic).reshape((-1, *self.action_space.shape))
-        actions = self.unscale_action(actions)
-        if not vectorized:
-            actions = actions.squeeze(axis=0)
-        return actions, state
-
     # ---- the update --------------------------------------------------------------------------------------------------
-    def _adam_scalars(self, lr: float, t: int) -> Tuple[float, float]:
-        b1, b2 = self.betas
-        pair = np.array([lr / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5], np.float32)
-        return float(pair[0]), float(pair[1])
-
-    def _workspace(self, B: int):
-        if B not in self._ws:
-            a, c, dev = self.actor, self.critic, self.device
-            D, A, nc = a.obs_dim, a.act_dim, c.n_critics
-            ld = D + A
-            sa, sc = a.stacks[0], c.stacks[0]
-            splits = max(1, min(64, B // 256))
-            e = lambda *shape: th.empty(*shape, device=dev)
-            i8 = lambda *shape: th.zeros(*shape, dtype=th.int8, device=dev)
-            hid = lambda s: e(max(1, B * s.hidden_per_row))
-            w = dict(ld=ld, splits=splits, X=e(B, ld), S=e(B, D), S2=e(B, D), rew=e(B), done=e(B), X2=e(B, ld), Xpi=e(B, ld),
-                     head=e(B, 2 * A), head2=e(B, 2 * A), dhead=e(B, 2 * A), logp=e(B), logp2=e(B), a=e(B, A), ls=e(B, A),
-                     om=e(B, A), bound=i8(B, A), q=e(nc, B), qt=e(nc, B), dq=e(nc, B), qpi=e(nc, B), seeds=e(nc, B), minq=e(B),
-                     argmin_t=i8(B), argmin_pi=i8(B), dX=[e(B, ld) for _ in range(nc)], hid_a=hid(sa), hid_a2=hid(sa),
-                     hid_c=[hid(sc) for _ in range(nc)], dhid_a=hid(sa), dhid_c=hid(sc), grads_a=e(sa.numel),
-                     grads_c=e(nc * sc.numel), scratch_c=e(splits, sc.numel))
-            # one K split (batches below 512 rows): the backward's slab IS the gradient, no reduction launch
-            w["part_a"] = w["grads_a"].view(1, -1) if splits == 1 else e(splits, sa.numel)
-            w["part_c"] = [w["grads_c"][i * sc.numel:(i + 1) * sc.numel].view(1, -1) if splits == 1 else e(splits, sc.numel)
-                           for i in range(nc)]
-            self._ws[B] = w
-        return self._ws[B]
+    def _extra_workspace(self, B: int, e, hid) -> Dict[str, Any]:
+        a, nc = self.actor, self.critic.n_critics
+        A, ld = a.act_dim, a.obs_dim + a.act_dim
+        i8 = lambda *shape: th.zeros(*shape, dtype=th.int8, device=self.device)
+        return dict(Xpi=e(B, ld), head=e(B, 2 * A), head2=e(B, 2 * A), dhead=e(B, 2 * A), logp=e(B), logp2=e(B), a=e(B, A),
+                    ls=e(B, A), om=e(B, A), bound=i8(B, A), qpi=e(nc, B), seeds=e(nc, B), minq=e(B), argmin_t=i8(B),
+                    argmin_pi=i8(B), dX=[e(B, ld) for _ in range(nc)], hid_a2=hid(a.stacks[0]))
 
     def update(self, ring: Optional[_Table], expert: Optional[_Table], idx_dev: th.Tensor, eps_dev: th.Tensor, n_new: int,
                n_steps: int, batch_size: int, gamma: float, tau: float, target_update_interval: int, target_entropy: float,
@@ -286,31 +199,24 @@ class SACPolicy:
         ent_coef_loss}, columns 2 and 3 pre-filled by the caller for a constant coefficient; `argmin_out` int8
         [n_steps, 2, B] receives which critic attained the target's and the actor's minimum. Nothing in the loop
         synchronises with the device or calls ATen."""
-        require_device(self.device)
         a, c, B, st = self.actor, self.critic, int(batch_size), L.stream()
-        w = self._workspace(B)
-        D, A, nc, ld, splits = a.obs_dim, a.act_dim, c.n_critics, w["ld"], w["splits"]
+        P, tables, critics_forward, critic_step, actor_step = self._begin_update(ring, expert, B, lr, st)
+        D, A, nc, ld, splits = a.obs_dim, a.act_dim, c.n_critics, P["ld"], P["splits"]
         sa, sc = a.stacks[0], c.stacks[0]
         na, ncrit = sa.numel, sc.numel
         call, ref = L.call, C.byref
-        P = {k: (v.data_ptr() if isinstance(v, th.Tensor) else v) for k, v in w.items()}
-        hid_c, part_c = [t.data_ptr() for t in w["hid_c"]], [t.data_ptr() for t in w["part_c"]]
-        dX = [t.data_ptr() for t in w["dX"]] + [None]
+        hid_c, dX = P["hid_c"], [t.data_ptr() for t in P["dX"]] + [None]
         on_a, on_c, tg_c = self._online.data_ptr(), self._online.data_ptr() + 4 * na, self._target.data_ptr()
-        m, v = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
         ent = self.ent_state.data_ptr()
         lec, ent_m, ent_v, alpha = ent, ent + 4, ent + 8, ent + 12
-        ring_args, exp_args = ((None,) * 5 + (0,) if t is None else
-                               (L.ptr(t.obs), L.ptr(t.next_obs), L.ptr(t.action), L.ptr(t.reward), L.ptr(t.done), t.rows)
-                               for t in (ring, expert))
         idx_ptr, eps_ptr, stats_ptr = idx_dev.data_ptr(), eps_dev.data_ptr(), stats.data_ptr()
         am_ptr = None if argmin_out is None else argmin_out.data_ptr()
         b1, b2 = float(self.betas[0]), float(self.betas[1])
         for s in range(n_steps):
             eps0, eps1 = eps_ptr + 4 * (2 * s) * B * A, eps_ptr + 4 * (2 * s + 1) * B * A
             am_t, am_pi = (P["argmin_t"], P["argmin_pi"]) if am_ptr is None else (am_ptr + 2 * s * B, am_ptr + (2 * s + 1) * B)
-            call("ia_td3_assemble", *ring_args, *exp_args, idx_ptr + 8 * s * B, B, int(n_new), D, A, ld, P["X"], P["S"],
-                 P["S2"], P["rew"], P["done"], st)
+            call("ia_td3_assemble", *tables, idx_ptr + 8 * s * B, B, int(n_new), D, A, ld, P["X"], P["S"], P["S2"], P["rew"],
+                 P["done"], st)
             # a_pi, logp = actor.action_log_prob(obs): [obs | a_pi] is the critics' input of the actor loss
             call("ia_mlp_forward", ref(sa.desc), on_a, P["S"], D, B, P["hid_a"], P["head"], L.ACT_NONE, st)
             call("ia_sac_sample", P["head"], eps0, P["S"], B, D, A, ld, P["Xpi"], P["logp"], P["a"], P["ls"], P["om"],
@@ -323,40 +229,20 @@ class SACPolicy:
             # target: y = r + (1 - d) gamma (min_i Qt_i(s', a') - alpha logp')
             call("ia_mlp_forward", ref(sa.desc), on_a, P["S2"], D, B, P["hid_a2"], P["head2"], L.ACT_NONE, st)
             call("ia_sac_sample", P["head2"], eps1, P["S2"], B, D, A, ld, P["X2"], P["logp2"], None, None, None, None, st)
-            for i in range(nc):
-                call("ia_mlp_forward", ref(sc.desc), tg_c + 4 * i * ncrit, P["X2"], ld, B, hid_c[i], P["qt"] + 4 * i * B,
-                     L.ACT_NONE, st)
-            for i in range(nc):
-                call("ia_mlp_forward", ref(sc.desc), on_c + 4 * i * ncrit, P["X"], ld, B, hid_c[i], P["q"] + 4 * i * B,
-                     L.ACT_NONE, st)
+            critics_forward(tg_c, P["X2"], P["qt"])
+            critics_forward(on_c, P["X"], P["q"])
             call("ia_sac_critic_loss", P["q"], P["qt"], P["logp2"], P["rew"], P["done"], alpha, B, nc, float(gamma), P["dq"],
                  None, am_t, stats_ptr + 16 * s, st)
-            for i in range(nc):
-                call("ia_mlp_backward", ref(sc.desc), on_c + 4 * i * ncrit, P["X"], ld, B, hid_c[i], P["dq"] + 4 * i * B,
-                     P["dhid_c"], part_c[i], splits, None, st)
-                if splits > 1:
-                    call("ia_reduce_partials", part_c[i], splits, ncrit, 1.0, 0, P["grads_c"] + 4 * i * ncrit, st)
-            self.critic_adam_steps += 1
-            step_size, bc2 = self._adam_scalars(lr, self.critic_adam_steps)
-            call("ia_dqn_adam_step", on_c, P["grads_c"], m + 4 * na, v + 4 * na, nc * ncrit, b1, b2, self.eps,
-                 self.weight_decay, step_size, bc2, st)
+            critic_step()
             # actor: loss = mean(alpha logp - min_i Q_i(s, a_pi)) with the updated critic
-            for i in range(nc):
-                call("ia_mlp_forward", ref(sc.desc), on_c + 4 * i * ncrit, P["Xpi"], ld, B, hid_c[i], P["qpi"] + 4 * i * B,
-                     L.ACT_NONE, st)
+            critics_forward(on_c, P["Xpi"], P["qpi"])
             call("ia_sac_min_seed", P["qpi"], B, nc, P["seeds"], P["minq"], am_pi, st)
             for i in range(nc):
                 call("ia_mlp_backward", ref(sc.desc), on_c + 4 * i * ncrit, P["Xpi"], ld, B, hid_c[i], P["seeds"] + 4 * i * B,
                      P["dhid_c"], P["scratch_c"], splits, dX[i], st)
             call("ia_sac_actor_seed", dX[0], dX[1] if nc == 2 else None, ld, D, P["a"], P["om"], eps0, P["ls"], P["bound"],
                  alpha, P["logp"], P["minq"], B, A, P["dhead"], stats_ptr + 16 * s + 4, st)
-            call("ia_mlp_backward", ref(sa.desc), on_a, P["S"], D, B, P["hid_a"], P["dhead"], P["dhid_a"], P["part_a"], splits,
-                 None, st)
-            if splits > 1:
-                call("ia_reduce_partials", P["part_a"], splits, na, 1.0, 0, P["grads_a"], st)
-            self.actor_adam_steps += 1
-            step_size, bc2 = self._adam_scalars(lr, self.actor_adam_steps)
-            call("ia_dqn_adam_step", on_a, P["grads_a"], m, v, na, b1, b2, self.eps, self.weight_decay, step_size, bc2, st)
+            actor_step(P["dhead"])
             # [SB3 SAC.train]: the step's index within the call (`step0`: this call's first step within a `train` call split)
             if (step0 + s) % target_update_interval == 0:
                 call("ia_polyak_update", on_c, tg_c, nc * ncrit, float(tau), st)
@@ -365,9 +251,8 @@ class SACPolicy:
 MlpPolicy = SACPolicy
 
 
-class SAC(TD3):
-    """[SB3 sac.SAC]. (Derives from `TD3` for the off-policy surface they share -- the constructor's checks, the collection
-    loop, action scaling and action noise; the policy, `train` and every default are SAC's.)"""
+class SAC(ContinuousOffPolicyAlgorithm):
+    """[SB3 sac.SAC]."""
 
     policy_aliases = {"MlpPolicy": SACPolicy}
 
@@ -394,26 +279,11 @@ class SAC(TD3):
                          gradient_steps=gradient_steps, action_noise=action_noise, replay_buffer_class=replay_buffer_class,
                          replay_buffer_kwargs=replay_buffer_kwargs, optimize_memory_usage=optimize_memory_usage,
                          stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, policy_kwargs=policy_kwargs,
-                         verbose=verbose, seed=seed, device=device, _init_setup_model=False)
-        del self.policy_delay, self.target_policy_noise, self.target_noise_clip   # TD3's, not SAC's
+                         verbose=verbose, seed=seed, device=device)
         if _init_setup_model:
             self._setup_model()
 
-    def _setup_model(self) -> None:
-        self.lr_schedule = _schedule(self.learning_rate)
-        if self.seed is not None:
-            set_random_seed(self.seed)
-            self.action_space.seed(self.seed)
-            if self.env is not None:
-                self.env.seed(self.seed)
-        if self.replay_buffer_class is None:
-            self.replay_buffer_class = ReplayBuffer
-        if self.replay_buffer is None:
-            self.replay_buffer = self.replay_buffer_class(
-                self.buffer_size, self.observation_space, self.action_space, device=self.device, n_envs=self.n_envs,
-                optimize_memory_usage=self.optimize_memory_usage, **self.replay_buffer_kwargs)
-        self.policy = self.policy_class(self.observation_space, self.action_space, self.lr_schedule,
-                                        **self.policy_kwargs).to(self.device)
+    def _bind_policy(self) -> None:
         self.actor, self.critic, self.critic_target = self.policy.actor, self.policy.critic, self.policy.critic_target
         # [SB3 SAC._setup_model]
         if self.target_entropy == "auto":
@@ -450,16 +320,8 @@ class SAC(TD3):
         """[SB3 SAC.train]: the index draws of all `gradient_steps` minibatches (NumPy's global stream), then the `eps` of all
         of them (torch's global generator) -- the two streams are independent, so each ends where SB3's interleaved draws
         leave it -- one upload of each, the steps, one read-back."""
-        self.policy.set_training_mode(True)
-        lr = self.lr_schedule(self._current_progress_remaining)
-        self.logger.record("train/learning_rate", lr)
-        rows = np.empty((gradient_steps, batch_size), np.int64)
-        n_new = batch_size
-        for s in range(gradient_steps):
-            rows[s], n_new = self.replay_buffer.sample_rows(batch_size)
-        eps = self.draw_eps(gradient_steps, batch_size)
-        self.last_sample_rows, self.last_n_new, self.last_eps = rows, n_new, eps
-        idx_dev = th.from_numpy(rows).to(self.device)
+        lr, rows, n_new, idx_dev = self._begin_train(gradient_steps, batch_size)
+        self.last_eps = eps = self.draw_eps(gradient_steps, batch_size)
         eps_dev = eps.to(self.device)
         learned = self.policy.ent_learned
         init = np.full((gradient_steps, 4), np.nan, np.float32)

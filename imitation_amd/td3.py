@@ -24,10 +24,9 @@ from torch import nn
 
 from imitation_amd import _lib as L
 from imitation_amd import spaces
-from imitation_amd.dqn import OffPolicyAlgorithm, ReplayBuffer, _device, _Table
 from imitation_amd.networks import require_device
+from imitation_amd.off_policy import OffPolicyAlgorithm, _Table, adam_kwargs, table_pointers
 from imitation_amd.policies import FlattenExtractor
-from imitation_amd.ppo import _schedule, set_random_seed
 
 
 class ActionNoise:
@@ -192,14 +191,16 @@ class ContinuousCritic(_Holder):
         self._flat = self._init_flat()
 
 
-class TD3Policy:
-    """[SB3 td3.policies.TD3Policy]: `_build` makes the actor, the actor target (which loads the actor's state), the critic
-    and the critic target (likewise), in that order; one Adam over the actor and one over the critic."""
+class ContinuousPolicy:
+    """What `TD3Policy` and `sac.SACPolicy` share: an actor and critics (with the targets a subclass names) whose parameters
+    lie in ONE flat online buffer [actor | critic] and one flat target buffer, one pair of Adam moment buffers over the
+    online one, SB3's action scaling and `predict`, the workspace of a batch size and the launch sequences both `update`
+    loops contain. A subclass supplies `holders`, `_build`, `actor_output`, `_extra_workspace` and `update`."""
 
-    def __init__(self, observation_space, action_space, lr_schedule, net_arch=None, activation_fn=nn.ReLU,
-                 features_extractor_class=FlattenExtractor, features_extractor_kwargs=None, normalize_images: bool = True,
-                 optimizer_class=th.optim.Adam, optimizer_kwargs=None, n_critics: int = 2,
-                 share_features_extractor: bool = False):
+    holders: Tuple[str, ...] = ()   # the networks in SB3's order; "<name>_target" starts as a copy of "<name>"
+
+    def __init__(self, observation_space, action_space, lr_schedule, net_arch, activation_fn, features_extractor_class,
+                 optimizer_class, optimizer_kwargs, n_critics, share_features_extractor):
         if features_extractor_class is not FlattenExtractor:
             raise NotImplementedError("only the flatten extractor (MlpPolicy) is implemented: no CNN extractor")
         if share_features_extractor:
@@ -207,36 +208,38 @@ class TD3Policy:
         if optimizer_class is not th.optim.Adam:
             raise NotImplementedError("only torch.optim.Adam is implemented")
         self.observation_space, self.action_space = observation_space, action_space
-        self.net_arch = [400, 300] if net_arch is None else net_arch
+        self.net_arch = net_arch
         actor_arch, critic_arch = get_actor_critic_arch(self.net_arch)
         self.activation_fn, self.n_critics = activation_fn, n_critics
-        self.optimizer_kwargs = dict(optimizer_kwargs or {})
-        unknown = set(self.optimizer_kwargs) - {"betas", "eps", "weight_decay"}
-        if unknown:
-            raise NotImplementedError(f"optimizer_kwargs {sorted(unknown)} are not implemented")
-        # [SB3 TD3Policy._build]: the draw order of torch's global generator
-        self.actor = Actor(observation_space, action_space, actor_arch, activation_fn)
-        self.actor_target = Actor(observation_space, action_space, actor_arch, activation_fn)
-        self.critic = ContinuousCritic(observation_space, action_space, critic_arch, activation_fn, n_critics)
-        self.critic_target = ContinuousCritic(observation_space, action_space, critic_arch, activation_fn, n_critics)
-        # online and target parameters as ONE flat buffer each, [actor | critic]: one polyak launch covers both
+        self.optimizer_kwargs, self.betas, self.eps, self.weight_decay = adam_kwargs(optimizer_kwargs)
+        self._build(actor_arch, critic_arch)   # (the draw order of torch's global generator)
+        # online parameters as ONE flat buffer [actor | critic] (one pair of moment buffers), the targets as another in
+        # the order of `holders`: one polyak launch covers all of them
         self._online = th.cat([self.actor._init_flat(), self.critic._init_flat()]).contiguous()
-        self._target = self._online.clone()
+        self._target = th.cat([getattr(self, name[:-len("_target")])._init_flat() for name in self._targets()]).contiguous()
         self.exp_avg, self.exp_avg_sq = th.zeros_like(self._online), th.zeros_like(self._online)
         self.lr = float(lr_schedule(1))
-        self.betas = tuple(self.optimizer_kwargs.get("betas", (0.9, 0.999)))
-        self.eps = float(self.optimizer_kwargs.get("eps", 1e-8))
-        self.weight_decay = float(self.optimizer_kwargs.get("weight_decay", 0.0))
         self.actor_adam_steps = self.critic_adam_steps = 0
         self.training = True
         self.squash_output = True
         self._ws: Dict[Any, Any] = {}
         self._bind()
 
+    def _build(self, actor_arch: List[int], critic_arch: List[int]) -> None:
+        """The networks named in `holders`, made in SB3's order."""
+        raise NotImplementedError
+
+    def _targets(self) -> List[str]:
+        return [name for name in self.holders if name.endswith("_target")]
+
     def _bind(self) -> None:
         na = self.actor.numel()
         self.actor._flat, self.critic._flat = self._online[:na], self._online[na:]
-        self.actor_target._flat, self.critic_target._flat = self._target[:na], self._target[na:]
+        off = 0
+        for name in self._targets():
+            h = getattr(self, name)
+            h._flat = self._target[off:off + h.numel()]
+            off += h.numel()
 
     @property
     def device(self) -> th.device:
@@ -253,24 +256,18 @@ class TD3Policy:
         self.training = mode
 
     def parameters(self):
-        for h in (self.actor, self.actor_target, self.critic, self.critic_target):
-            yield from h.parameters()
+        for name in self.holders:
+            yield from getattr(self, name).parameters()
 
     def state_dict(self) -> Dict[str, th.Tensor]:
         out: Dict[str, th.Tensor] = {}
-        for name in ("actor", "actor_target", "critic", "critic_target"):
+        for name in self.holders:
             out.update({f"{name}.{k}": v for k, v in getattr(self, name).state_dict().items()})
         return out
 
     def load_state_dict(self, sd) -> None:
-        for name in ("actor", "actor_target", "critic", "critic_target"):
+        for name in self.holders:
             getattr(self, name).load_state_dict({k[len(name) + 1:]: v for k, v in sd.items() if k.startswith(name + ".")})
-
-    def optimizer_state(self) -> Dict[str, th.Tensor]:
-        """Adam's moments per optimiser, in the layout of the parameters."""
-        na = self.actor.numel()
-        return {"actor.exp_avg": self.exp_avg[:na], "actor.exp_avg_sq": self.exp_avg_sq[:na],
-                "critic.exp_avg": self.exp_avg[na:], "critic.exp_avg_sq": self.exp_avg_sq[na:]}
 
     # ---- [SB3 BasePolicy] actions ------------------------------------------------------------------------------------
     def scale_action(self, action: np.ndarray) -> np.ndarray:
@@ -283,17 +280,12 @@ class TD3Policy:
         low, high = self.action_space.low, self.action_space.high
         return low + (0.5 * (scaled_action + 1.0) * (high - low))
 
-    def actor_output(self, observation: np.ndarray) -> np.ndarray:
-        """mu of host observations (one upload, one read-back)."""
-        obs = np.ascontiguousarray(observation, np.float32).reshape(-1, self.actor.obs_dim)
-        return self.actor.forward(th.from_numpy(obs).to(self.device)).cpu().numpy()
-
     def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
-        """[SB3 BasePolicy.predict] of a squashing policy: the actor's output, unscaled to the action bounds."""
+        """[SB3 BasePolicy.predict] of a squashing policy: the actor's action, unscaled to the action bounds."""
         self.set_training_mode(False)
         observation = np.asarray(observation)
         vectorized = observation.shape != tuple(self.observation_space.shape)
-        actions = self.actor_output(observation).reshape((-1, *self.action_space.shape))
+        actions = self.actor_output(observation, deterministic).reshape((-1, *self.action_space.shape))
         actions = self.unscale_action(actions)
         if not vectorized:
             actions = actions.squeeze(axis=0)
@@ -314,10 +306,10 @@ class TD3Policy:
             splits = max(1, min(64, B // 256))
             e = lambda *shape: th.empty(*shape, device=dev)
             hid = lambda s: e(max(1, B * s.hidden_per_row))
-            w = dict(ld=ld, splits=splits, X=e(B, ld), S=e(B, D), S2=e(B, D), rew=e(B), done=e(B), X2=e(B, ld), mu_t=e(B, A),
-                     mu=e(B, A), dmu=e(B, A), q=e(nc, B), qt=e(nc, B), dq=e(nc, B), q1=e(1, B), ones=th.ones(B, device=dev),
-                     dX=e(B, ld), hid_a=hid(sa), hid_c=[hid(sc) for _ in range(nc)], dhid_a=hid(sa), dhid_c=hid(sc),
-                     grads_a=e(sa.numel), grads_c=e(nc * sc.numel), scratch_c=e(splits, sc.numel))
+            w = dict(ld=ld, splits=splits, X=e(B, ld), S=e(B, D), S2=e(B, D), rew=e(B), done=e(B), X2=e(B, ld), q=e(nc, B),
+                     qt=e(nc, B), dq=e(nc, B), hid_a=hid(sa), hid_c=[hid(sc) for _ in range(nc)], dhid_a=hid(sa),
+                     dhid_c=hid(sc), grads_a=e(sa.numel), grads_c=e(nc * sc.numel), scratch_c=e(splits, sc.numel))
+            w.update(self._extra_workspace(B, e, hid))
             # one K split (batches below 512 rows): the backward's slab IS the gradient, no reduction launch
             w["part_a"] = w["grads_a"].view(1, -1) if splits == 1 else e(splits, sa.numel)
             w["part_c"] = [w["grads_c"][i * sc.numel:(i + 1) * sc.numel].view(1, -1) if splits == 1 else e(splits, sc.numel)
@@ -325,47 +317,37 @@ class TD3Policy:
             self._ws[B] = w
         return self._ws[B]
 
-    def update(self, ring: Optional[_Table], expert: Optional[_Table], idx_dev: th.Tensor, noise_dev: th.Tensor, n_new: int,
-               n_steps: int, batch_size: int, gamma: float, tau: float, policy_delay: int, noise_clip: float,
-               n_updates: int, lr: float, stats: th.Tensor) -> List[bool]:
-        """`n_steps` gradient steps of [SB3 TD3.train]. `idx_dev` int64 [n_steps, B], `noise_dev` float32 [n_steps, B, A]
-        (unclipped), `n_updates` the learner's count BEFORE this call, `stats` float32 [n_steps, 2] with NaN in column 1.
-        Returns which steps updated the actor. Nothing in the loop synchronises with the device or calls ATen."""
+    def _extra_workspace(self, B: int, e, hid) -> Dict[str, Any]:
+        """The learner's own buffers of a batch of `B` rows (`e(*shape)`: an fp32 device buffer; `hid(stack)`: a stack's
+        hidden activations)."""
+        raise NotImplementedError
+
+    def _begin_update(self, ring: Optional[_Table], expert: Optional[_Table], B: int, lr: float, st):
+        """What both `update` loops start from -> (P, tables, critics_forward, critic_step, actor_step): the workspace of
+        `B` rows as raw pointers (`hid_c` and `part_c` as lists of them), the pointers and row counts of the two tables
+        (a table no row of the batch comes from may be absent) and the launch sequences the two steps share, bound to
+        these buffers and to stream `st` so that a step pays one call for each:
+          critics_forward(params, x, out)  the critics at `params` (n_critics blocks back to back) on input `x` -> `out`
+          critic_step()                    critics' backward from `dq`, the K-split reduction if any, their Adam step
+          actor_step(seed)                 the actor's backward from `seed`, the reduction if any, its Adam step"""
         require_device(self.device)
-        a, c, B, st = self.actor, self.critic, int(batch_size), L.stream()
         w = self._workspace(B)
-        D, A, nc, ld, splits = a.obs_dim, a.act_dim, c.n_critics, w["ld"], w["splits"]
-        sa, sc = a.stacks[0], c.stacks[0]
-        na, ncrit = sa.numel, sc.numel
+        sa, sc = self.actor.stacks[0], self.critic.stacks[0]
+        D, nc, ld, splits, na, ncrit = self.actor.obs_dim, self.critic.n_critics, w["ld"], w["splits"], sa.numel, sc.numel
         call, ref = L.call, C.byref
         P = {k: (v.data_ptr() if isinstance(v, th.Tensor) else v) for k, v in w.items()}
-        hid_c, part_c = [t.data_ptr() for t in w["hid_c"]], [t.data_ptr() for t in w["part_c"]]
+        hid_c = P["hid_c"] = [t.data_ptr() for t in w["hid_c"]]
+        part_c = P["part_c"] = [t.data_ptr() for t in w["part_c"]]
         on_a, on_c = self._online.data_ptr(), self._online.data_ptr() + 4 * na
-        tg_a, tg_c = self._target.data_ptr(), self._target.data_ptr() + 4 * na
         m, v = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
-        # (a table no row of the batch comes from may be absent)
-        ring_args, exp_args = ((None,) * 5 + (0,) if t is None else
-                               (L.ptr(t.obs), L.ptr(t.next_obs), L.ptr(t.action), L.ptr(t.reward), L.ptr(t.done), t.rows)
-                               for t in (ring, expert))
-        idx_ptr, noise_ptr, stats_ptr = idx_dev.data_ptr(), noise_dev.data_ptr(), stats.data_ptr()
         b1, b2 = float(self.betas[0]), float(self.betas[1])
-        actor_steps: List[bool] = []
-        for s in range(n_steps):
-            n_updates += 1
-            call("ia_td3_assemble", *ring_args, *exp_args, idx_ptr + 8 * s * B, B, int(n_new), D, A, ld, P["X"], P["S"],
-                 P["S2"], P["rew"], P["done"], st)
-            # target: y = r + (1 - d) gamma min_i Qt_i(s', clamp(mu_t(s') + clamp(noise)))
-            call("ia_mlp_forward", ref(sa.desc), tg_a, P["S2"], D, B, P["hid_a"], P["mu_t"], L.ACT_TANH, st)
-            call("ia_td3_target_input", P["S2"], P["mu_t"], noise_ptr + 4 * s * B * A, B, D, A, ld, float(noise_clip), P["X2"],
-                 st)
-            for i in range(nc):   # the twin critics: two parameter blocks over ONE input tile
-                call("ia_mlp_forward", ref(sc.desc), tg_c + 4 * i * ncrit, P["X2"], ld, B, hid_c[i], P["qt"] + 4 * i * B,
-                     L.ACT_NONE, st)
+
+        def critics_forward(params, x, out):   # the twin critics: two parameter blocks over ONE input tile
             for i in range(nc):
-                call("ia_mlp_forward", ref(sc.desc), on_c + 4 * i * ncrit, P["X"], ld, B, hid_c[i], P["q"] + 4 * i * B,
-                     L.ACT_NONE, st)
-            call("ia_td3_critic_loss", P["q"], P["qt"], P["rew"], P["done"], B, nc, float(gamma), P["dq"], None,
-                 stats_ptr + 8 * s, st)
+                call("ia_mlp_forward", ref(sc.desc), params + 4 * i * ncrit, x, ld, B, hid_c[i], out + 4 * i * B, L.ACT_NONE,
+                     st)
+
+        def critic_step():
             for i in range(nc):
                 call("ia_mlp_backward", ref(sc.desc), on_c + 4 * i * ncrit, P["X"], ld, B, hid_c[i], P["dq"] + 4 * i * B,
                      P["dhid_c"], part_c[i], splits, None, st)
@@ -375,23 +357,96 @@ class TD3Policy:
             step_size, bc2 = self._adam_scalars(lr, self.critic_adam_steps)
             call("ia_dqn_adam_step", on_c, P["grads_c"], m + 4 * na, v + 4 * na, nc * ncrit, b1, b2, self.eps,
                  self.weight_decay, step_size, bc2, st)
+
+        def actor_step(seed):
+            call("ia_mlp_backward", ref(sa.desc), on_a, P["S"], D, B, P["hid_a"], seed, P["dhid_a"], P["part_a"], splits, None,
+                 st)
+            if splits > 1:
+                call("ia_reduce_partials", P["part_a"], splits, na, 1.0, 0, P["grads_a"], st)
+            self.actor_adam_steps += 1
+            step_size, bc2 = self._adam_scalars(lr, self.actor_adam_steps)
+            call("ia_dqn_adam_step", on_a, P["grads_a"], m, v, na, b1, b2, self.eps, self.weight_decay, step_size, bc2, st)
+
+        return P, table_pointers(ring) + table_pointers(expert), critics_forward, critic_step, actor_step
+
+
+class TD3Policy(ContinuousPolicy):
+    """[SB3 td3.policies.TD3Policy]: `_build` makes the actor, the actor target (which loads the actor's state), the critic
+    and the critic target (likewise), in that order; one Adam over the actor and one over the critic."""
+
+    holders = ("actor", "actor_target", "critic", "critic_target")
+
+    def __init__(self, observation_space, action_space, lr_schedule, net_arch=None, activation_fn=nn.ReLU,
+                 features_extractor_class=FlattenExtractor, features_extractor_kwargs=None, normalize_images: bool = True,
+                 optimizer_class=th.optim.Adam, optimizer_kwargs=None, n_critics: int = 2,
+                 share_features_extractor: bool = False):
+        super().__init__(observation_space, action_space, lr_schedule, [400, 300] if net_arch is None else net_arch,
+                         activation_fn, features_extractor_class, optimizer_class, optimizer_kwargs, n_critics,
+                         share_features_extractor)
+
+    def _build(self, actor_arch: List[int], critic_arch: List[int]) -> None:
+        # [SB3 TD3Policy._build]
+        space, fn = (self.observation_space, self.action_space), self.activation_fn
+        self.actor = Actor(*space, actor_arch, fn)
+        self.actor_target = Actor(*space, actor_arch, fn)
+        self.critic = ContinuousCritic(*space, critic_arch, fn, self.n_critics)
+        self.critic_target = ContinuousCritic(*space, critic_arch, fn, self.n_critics)
+
+    def optimizer_state(self) -> Dict[str, th.Tensor]:
+        """Adam's moments per optimiser, in the layout of the parameters."""
+        na = self.actor.numel()
+        return {"actor.exp_avg": self.exp_avg[:na], "actor.exp_avg_sq": self.exp_avg_sq[:na],
+                "critic.exp_avg": self.exp_avg[na:], "critic.exp_avg_sq": self.exp_avg_sq[na:]}
+
+    def actor_output(self, observation: np.ndarray, deterministic: bool = False) -> np.ndarray:
+        """mu of host observations (one upload, one read-back); the policy is deterministic either way."""
+        obs = np.ascontiguousarray(observation, np.float32).reshape(-1, self.actor.obs_dim)
+        return self.actor.forward(th.from_numpy(obs).to(self.device)).cpu().numpy()
+
+    def _extra_workspace(self, B: int, e, hid) -> Dict[str, Any]:
+        A, ld = self.actor.act_dim, self.actor.obs_dim + self.actor.act_dim
+        return dict(mu_t=e(B, A), mu=e(B, A), dmu=e(B, A), q1=e(1, B), ones=th.ones(B, device=self.device), dX=e(B, ld))
+
+    def update(self, ring: Optional[_Table], expert: Optional[_Table], idx_dev: th.Tensor, noise_dev: th.Tensor, n_new: int,
+               n_steps: int, batch_size: int, gamma: float, tau: float, policy_delay: int, noise_clip: float,
+               n_updates: int, lr: float, stats: th.Tensor) -> List[bool]:
+        """`n_steps` gradient steps of [SB3 TD3.train]. `idx_dev` int64 [n_steps, B], `noise_dev` float32 [n_steps, B, A]
+        (unclipped), `n_updates` the learner's count BEFORE this call, `stats` float32 [n_steps, 2] with NaN in column 1.
+        Returns which steps updated the actor. Nothing in the loop synchronises with the device or calls ATen."""
+        a, c, B, st = self.actor, self.critic, int(batch_size), L.stream()
+        P, tables, critics_forward, critic_step, actor_step = self._begin_update(ring, expert, B, lr, st)
+        D, A, nc, ld, splits = a.obs_dim, a.act_dim, c.n_critics, P["ld"], P["splits"]
+        sa, sc = a.stacks[0], c.stacks[0]
+        na, ncrit = sa.numel, sc.numel
+        call, ref = L.call, C.byref
+        on_a, on_c = self._online.data_ptr(), self._online.data_ptr() + 4 * na
+        tg_a, tg_c = self._target.data_ptr(), self._target.data_ptr() + 4 * na
+        idx_ptr, noise_ptr, stats_ptr = idx_dev.data_ptr(), noise_dev.data_ptr(), stats.data_ptr()
+        actor_steps: List[bool] = []
+        for s in range(n_steps):
+            n_updates += 1
+            call("ia_td3_assemble", *tables, idx_ptr + 8 * s * B, B, int(n_new), D, A, ld, P["X"], P["S"], P["S2"], P["rew"],
+                 P["done"], st)
+            # target: y = r + (1 - d) gamma min_i Qt_i(s', clamp(mu_t(s') + clamp(noise)))
+            call("ia_mlp_forward", ref(sa.desc), tg_a, P["S2"], D, B, P["hid_a"], P["mu_t"], L.ACT_TANH, st)
+            call("ia_td3_target_input", P["S2"], P["mu_t"], noise_ptr + 4 * s * B * A, B, D, A, ld, float(noise_clip), P["X2"],
+                 st)
+            critics_forward(tg_c, P["X2"], P["qt"])
+            critics_forward(on_c, P["X"], P["q"])
+            call("ia_td3_critic_loss", P["q"], P["qt"], P["rew"], P["done"], B, nc, float(gamma), P["dq"], None,
+                 stats_ptr + 8 * s, st)
+            critic_step()
             actor_steps.append(n_updates % policy_delay == 0)
             if not actor_steps[-1]:
                 continue
             # actor: loss = -mean Q_1(s, mu(s)); its gradient enters the actor through the critic's dX
             call("ia_mlp_forward", ref(sa.desc), on_a, P["S"], D, B, P["hid_a"], P["mu"], L.ACT_TANH, st)
             call("ia_td3_actor_input", P["mu"], B, D, A, ld, P["X"], st)
-            call("ia_mlp_forward", ref(sc.desc), on_c, P["X"], ld, B, hid_c[0], P["q1"], L.ACT_NONE, st)
-            call("ia_mlp_backward", ref(sc.desc), on_c, P["X"], ld, B, hid_c[0], P["ones"], P["dhid_c"], P["scratch_c"], splits,
-                 P["dX"], st)
+            call("ia_mlp_forward", ref(sc.desc), on_c, P["X"], ld, B, P["hid_c"][0], P["q1"], L.ACT_NONE, st)
+            call("ia_mlp_backward", ref(sc.desc), on_c, P["X"], ld, B, P["hid_c"][0], P["ones"], P["dhid_c"], P["scratch_c"],
+                 splits, P["dX"], st)
             call("ia_td3_actor_seed", P["q1"], P["dX"], P["mu"], B, D, A, ld, P["dmu"], stats_ptr + 8 * s + 4, st)
-            call("ia_mlp_backward", ref(sa.desc), on_a, P["S"], D, B, P["hid_a"], P["dmu"], P["dhid_a"], P["part_a"], splits,
-                 None, st)
-            if splits > 1:
-                call("ia_reduce_partials", P["part_a"], splits, na, 1.0, 0, P["grads_a"], st)
-            self.actor_adam_steps += 1
-            step_size, bc2 = self._adam_scalars(lr, self.actor_adam_steps)
-            call("ia_dqn_adam_step", on_a, P["grads_a"], m, v, na, b1, b2, self.eps, self.weight_decay, step_size, bc2, st)
+            actor_step(P["dmu"])
             # [SB3 utils.polyak_update] of critic and actor: one launch over [actor | critic]
             call("ia_polyak_update", on_a, tg_a, na + nc * ncrit, float(tau), st)
         return actor_steps
@@ -400,23 +455,13 @@ class TD3Policy:
 MlpPolicy = TD3Policy
 
 
-class TD3(OffPolicyAlgorithm):
-    """[SB3 td3.TD3]."""
+class ContinuousOffPolicyAlgorithm(OffPolicyAlgorithm):
+    """What `TD3` and `sac.SAC` share of [SB3 OffPolicyAlgorithm] for Box actions: `train_freq` in steps or episodes, the
+    action noise, action scaling around the ring (it stores the SCALED action) and the collection branches."""
 
-    policy_aliases = {"MlpPolicy": TD3Policy}
-
-    def __init__(self, policy, env, learning_rate=1e-3, buffer_size: int = 1_000_000, learning_starts: int = 100,
-                 batch_size: int = 100, tau: float = 0.005, gamma: float = 0.99, train_freq=(1, "episode"),
-                 gradient_steps: int = -1, action_noise=None, replay_buffer_class=None,
-                 replay_buffer_kwargs: Optional[Dict[str, Any]] = None, optimize_memory_usage: bool = False,
-                 policy_delay: int = 2, target_policy_noise: float = 0.2, target_noise_clip: float = 0.5,
-                 stats_window_size: int = 100, tensorboard_log=None, policy_kwargs: Optional[Dict[str, Any]] = None,
-                 verbose: int = 0, seed: Optional[int] = None, device="auto", _init_setup_model: bool = True):
-        if isinstance(policy, str):
-            if policy not in self.policy_aliases:
-                raise NotImplementedError(f"policy {policy!r}: only 'MlpPolicy' is implemented for TD3 / DDPG "
-                                          "(no CNN or multi-input extractor)")
-            policy = self.policy_aliases[policy]
+    def __init__(self, *, policy, env, learning_rate, buffer_size, learning_starts, batch_size, tau, gamma, train_freq,
+                 gradient_steps, action_noise, replay_buffer_class, replay_buffer_kwargs, optimize_memory_usage,
+                 stats_window_size, tensorboard_log, policy_kwargs, verbose, seed, device):
         if tensorboard_log is not None:
             raise NotImplementedError("tensorboard logging is not implemented")
         # [SB3 OffPolicyAlgorithm._convert_train_freq]
@@ -428,63 +473,18 @@ class TD3(OffPolicyAlgorithm):
             raise ValueError(f"The frequency of `train_freq` must be an integer and not {train_freq[0]}")
         if action_noise is not None and not (callable(action_noise) and hasattr(action_noise, "reset")):
             raise TypeError("action_noise must be None or an object with __call__ and reset")
-        self.policy_class = policy
-        self.policy_kwargs = dict(policy_kwargs or {})
-        if self.policy_kwargs.get("use_sde") or "sde_sample_freq" in self.policy_kwargs:
+        if (policy_kwargs or {}).get("use_sde") or "sde_sample_freq" in (policy_kwargs or {}):
             raise NotImplementedError("gSDE is not implemented")
-        self.device = _device(device)
-        self.learning_rate, self.buffer_size, self.learning_starts = learning_rate, buffer_size, learning_starts
-        self.batch_size, self.tau, self.gamma = batch_size, tau, gamma
-        self.train_freq, self.gradient_steps = (int(train_freq[0]), train_freq[1]), gradient_steps
+        super().__init__(policy=policy, env=env, learning_rate=learning_rate, buffer_size=buffer_size,
+                         learning_starts=learning_starts, batch_size=batch_size, tau=tau, gamma=gamma,
+                         train_freq=(int(train_freq[0]), train_freq[1]), gradient_steps=gradient_steps,
+                         replay_buffer_class=replay_buffer_class, replay_buffer_kwargs=replay_buffer_kwargs,
+                         optimize_memory_usage=optimize_memory_usage, stats_window_size=stats_window_size,
+                         policy_kwargs=policy_kwargs, verbose=verbose, seed=seed, device=device)
         self.action_noise = action_noise
-        self.replay_buffer_class = replay_buffer_class
-        self.replay_buffer_kwargs = dict(replay_buffer_kwargs or {})
-        self.optimize_memory_usage = optimize_memory_usage
-        self.policy_delay, self.target_policy_noise = policy_delay, target_policy_noise
-        self.target_noise_clip = target_noise_clip
-        self.seed, self.verbose = seed, verbose
-        self.num_timesteps = 0
-        self._total_timesteps = 0
-        self._num_timesteps_at_start = 0
-        self._n_updates = 0
-        self._episode_num = 0
-        self._current_progress_remaining = 1.0
-        self._last_obs = None
-        self._last_episode_starts = None
-        self._stats_window_size = stats_window_size
-        self.ep_info_buffer = None
-        self._logger = None
-        self._custom_logger = False
-        self.start_time = 0
-        self.env = env
-        self.policy: Optional[TD3Policy] = None
-        self.replay_buffer: Optional[ReplayBuffer] = None
-        self.last_action_branch: Optional[str] = None   # "warmup" / "policy" of the latest `_sample_action`
-        if env is not None:
-            self.observation_space, self.action_space, self.n_envs = env.observation_space, env.action_space, env.num_envs
-            if isinstance(self.action_space, spaces.Box):
-                assert np.all(np.isfinite(np.array([self.action_space.low, self.action_space.high]))), \
-                    "Continuous action space must have a finite lower and upper bound"
-        if _init_setup_model:
-            self._setup_model()
-
-    def _setup_model(self) -> None:
-        self.lr_schedule = _schedule(self.learning_rate)
-        if self.seed is not None:
-            set_random_seed(self.seed)
-            self.action_space.seed(self.seed)
-            if self.env is not None:
-                self.env.seed(self.seed)
-        if self.replay_buffer_class is None:
-            self.replay_buffer_class = ReplayBuffer
-        if self.replay_buffer is None:
-            self.replay_buffer = self.replay_buffer_class(
-                self.buffer_size, self.observation_space, self.action_space, device=self.device, n_envs=self.n_envs,
-                optimize_memory_usage=self.optimize_memory_usage, **self.replay_buffer_kwargs)
-        self.policy = self.policy_class(self.observation_space, self.action_space, self.lr_schedule,
-                                        **self.policy_kwargs).to(self.device)
-        self.actor, self.actor_target = self.policy.actor, self.policy.actor_target
-        self.critic, self.critic_target = self.policy.critic, self.policy.critic_target
+        if env is not None and isinstance(self.action_space, spaces.Box):
+            assert np.all(np.isfinite(np.array([self.action_space.low, self.action_space.high]))), \
+                "Continuous action space must have a finite lower and upper bound"
 
     def _setup_learn(self, total_timesteps: int, callback, reset_num_timesteps: bool):
         # [SB3 OffPolicyAlgorithm._setup_learn]: one noise object per environment
@@ -515,6 +515,37 @@ class TD3(OffPolicyAlgorithm):
             kwargs = dict(indices=[env_index]) if n_envs > 1 else {}
             self.action_noise.reset(**kwargs)
 
+
+class TD3(ContinuousOffPolicyAlgorithm):
+    """[SB3 td3.TD3]."""
+
+    policy_aliases = {"MlpPolicy": TD3Policy}
+
+    def __init__(self, policy, env, learning_rate=1e-3, buffer_size: int = 1_000_000, learning_starts: int = 100,
+                 batch_size: int = 100, tau: float = 0.005, gamma: float = 0.99, train_freq=(1, "episode"),
+                 gradient_steps: int = -1, action_noise=None, replay_buffer_class=None,
+                 replay_buffer_kwargs: Optional[Dict[str, Any]] = None, optimize_memory_usage: bool = False,
+                 policy_delay: int = 2, target_policy_noise: float = 0.2, target_noise_clip: float = 0.5,
+                 stats_window_size: int = 100, tensorboard_log=None, policy_kwargs: Optional[Dict[str, Any]] = None,
+                 verbose: int = 0, seed: Optional[int] = None, device="auto", _init_setup_model: bool = True):
+        if isinstance(policy, str) and policy not in self.policy_aliases:
+            raise NotImplementedError(f"policy {policy!r}: only 'MlpPolicy' is implemented for TD3 / DDPG "
+                                      "(no CNN or multi-input extractor)")
+        super().__init__(policy=policy, env=env, learning_rate=learning_rate, buffer_size=buffer_size,
+                         learning_starts=learning_starts, batch_size=batch_size, tau=tau, gamma=gamma, train_freq=train_freq,
+                         gradient_steps=gradient_steps, action_noise=action_noise, replay_buffer_class=replay_buffer_class,
+                         replay_buffer_kwargs=replay_buffer_kwargs, optimize_memory_usage=optimize_memory_usage,
+                         stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, policy_kwargs=policy_kwargs,
+                         verbose=verbose, seed=seed, device=device)
+        self.policy_delay, self.target_policy_noise = policy_delay, target_policy_noise
+        self.target_noise_clip = target_noise_clip
+        if _init_setup_model:
+            self._setup_model()
+
+    def _bind_policy(self) -> None:
+        self.actor, self.actor_target = self.policy.actor, self.policy.actor_target
+        self.critic, self.critic_target = self.policy.critic, self.policy.critic_target
+
     def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "TD3",
               reset_num_timesteps: bool = True, progress_bar: bool = False):
         return super().learn(total_timesteps, callback, log_interval, tb_log_name, reset_num_timesteps, progress_bar)
@@ -532,16 +563,8 @@ class TD3(OffPolicyAlgorithm):
         """[SB3 TD3.train]: the index draws of all `gradient_steps` minibatches (NumPy's global stream), then the noise of
         all of them (torch's global generator) -- the two streams are independent, so each ends where SB3's interleaved
         draws leave it -- one upload of each, the steps, one read-back."""
-        self.policy.set_training_mode(True)
-        lr = self.lr_schedule(self._current_progress_remaining)
-        self.logger.record("train/learning_rate", lr)
-        rows = np.empty((gradient_steps, batch_size), np.int64)
-        n_new = batch_size
-        for s in range(gradient_steps):
-            rows[s], n_new = self.replay_buffer.sample_rows(batch_size)
-        noise = self.draw_target_noise(gradient_steps, batch_size)
-        self.last_sample_rows, self.last_n_new, self.last_target_noise = rows, n_new, noise
-        idx_dev = th.from_numpy(rows).to(self.device)
+        lr, rows, n_new, idx_dev = self._begin_train(gradient_steps, batch_size)
+        self.last_target_noise = noise = self.draw_target_noise(gradient_steps, batch_size)
         noise_dev = noise.to(self.device)
         stats = th.full((gradient_steps, 2), float("nan"), device=self.device)
         self.last_actor_steps = []

@@ -278,7 +278,7 @@ class RewardVecEnvWrapper(VecEnvWrapper):
         self.reward_fn = reward_fn
         self._old_obs = None
         self._actions = None
-        # `dqn.RewardStepSource` (off-policy generators): `step_wait` then computes no reward -- the learner ring's `add`
+        # `step_source.RewardStepSource` (off-policy generators): `step_wait` then computes no reward -- the learner ring's `add`
         # relabels and stores the step in one launch -- and the episode bookkeeping is deferred (`flush_rewards`)
         self.step_source = None
         self._pending_dones: List[np.ndarray] = []

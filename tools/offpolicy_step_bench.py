@@ -1,5 +1,5 @@
 """Microseconds per environment step of `AdversarialTrainer.train_gen` with an off-policy generator on the GPU: the fused
-step (`dqn.RewardStepSource`, one `ia_offpolicy_step` launch per step, csrc/offpolicy.hip) against the per-step host path
+step (`step_source.RewardStepSource`, one `ia_offpolicy_step` launch per step, csrc/offpolicy.hip) against the per-step host path
 (`IA_OFFPOLICY_FUSED=0`: the wrapper's `predict_processed` with its read-back, then the ring's copies), alternating in one
 process on one box. One JSON line per configuration:
 
